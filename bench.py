@@ -14,9 +14,16 @@ before the timed region.
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --single-process                            (one process, N devices)
 
-Rank 0 prints ONE JSON line.  `roofline` covers the dominant kernel, timed live with hipEvents
-on the library's stream inside the timed region; `cpu_baseline` times the oracle's faithful
-C++ restatement of MipNerfModel.GetGradient on the host (rank 0, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline figures: `value`, `ms_per_step` and the `roofline` of the dominant MLP kernel, timed live
+with hipEvents on the library's stream inside the timed region.  `--full` adds every secondary
+measurement, each a run of its own: the per-kernel breakdown, the other precision modes, the other
+BASELINE configurations (`config0`, `config3`, `config4_1gpu`, `config5`, `llff_1gpu`), the
+PCIe-inclusive API path, the render throughput, the integrator's HBM roofline, and `cpu_baseline` /
+`psnr_vs_ref`, which run the oracle's faithful C++ restatement of MipNerfModel.GetGradient on the
+host (rank 0, N = 1 only); the `--no-*` options trim a `--full` run.  `--dump-outputs DIR` writes
+what the last timed step computed (gradients, parameters after Adam, composited colours, loss) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -86,6 +93,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement (per-kernel breakdown, other precisions and "
+                        "configurations, API path, render, integrator roofline, CPU baseline, PSNR vs ref); "
+                        "the --no-* options trim it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32)")
     p.add_argument("--global-batch", type=int, default=None,
                    help="rays per step over all GPUs (default: 1024 at N=1 = configs[1]; 65536 at N>1 = configs[3], "
                         "strong scaling; LLFF: 512 per GPU = configs[4]'s per-GPU shape)")
@@ -110,6 +123,8 @@ def parse():
                    help="N>1 gradient all-reduce: torch.distributed (RCCL) or the C ABI's nof_dp_* (RCCL)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-integrator", action="store_true")
+    p.add_argument("--no-api-path", action="store_true",
+                   help="skip the host-buffer API path and the render throughput legs")
     p.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-baseline work (both legs)")
     a = p.parse_args()
     if a.rays is not None:
@@ -117,6 +132,10 @@ def parse():
             p.error("--rays and --global-batch are exclusive")
         a.global_batch = a.rays * a.gpus
     a.global_batch_fixed = a.rays is None  # strong scaling unless the per-GPU size was given
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # a plain run measures the headline only
+        a.no_alt = a.no_config4 = a.no_config5 = a.no_cpu_baseline = a.no_integrator = a.no_api_path = True
     return a
 
 
@@ -363,6 +382,26 @@ def workload_name(a, B):
     return "BASELINE configs[2]" if a.samples == [64, 128] else "Lego-shaped"
 
 
+def dump_outputs(nof, out_dir, models, ranks, many):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy files.
+    Per model (one per rank or device; `_rank<r>` is appended to the names when there are several): the
+    flat gradient arena (`grads`), the flat parameters after the Adam step (`params`), each level's
+    composited colours of the step's last micro-batch (`comp_rgb_level<l>`) and its loss (`loss`).
+    The 8x256 network's arenas are 2.4 MB each; the colours are 12 bytes per ray."""
+    os.makedirs(out_dir, exist_ok=True)
+    for r, m in zip(ranks, models):
+        tag = f"_rank{r}" if many else ""
+        pptr, P = m.mlp.flat_params()
+        gptr, Pg = m.mlp.flat_grads()
+        arrays = {"params": nof.to_numpy(pptr, (P,)), "grads": nof.to_numpy(gptr, (Pg,)),
+                  "loss": np.array([m.loss()], np.float32)}
+        for l in range(m.config.num_levels):
+            cptr, shp = m.level_view(l)["comp_rgb"]
+            arrays[f"comp_rgb_level{l}"] = nof.to_numpy(cptr, shp)
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, name + tag + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def chunks(n, m):
     """[lo, hi) micro-batches of at most m rays covering n."""
     return [(lo, min(n, lo + m)) for lo in range(0, n, m)]
@@ -440,11 +479,13 @@ def main():
         dist.broadcast_object_list(obj, src=0)
         native = [NativeDP.init_rank(obj[0], world, rank, dev_idx)]
 
-    def measure(prec, B_run=None, steps=None, warmup=None, timers_on=True, scene=None, smp=None, net=None):
+    def measure(prec, B_run=None, steps=None, warmup=None, timers_on=True, scene=None, smp=None, net=None,
+                dump=None):
         """W untimed + K timed training steps of one precision mode over the global batch (each
-        rank's shard in micro-batches accumulated into one gradient, one all-reduce), then a short
-        untimed pass with every kernel class event-timed (the per-kernel breakdown); returns
-        (s, timing, psnr, in_sync).  Inside the timed region only the MLP kernel classes (mlp_fwd,
+        rank's shard in micro-batches accumulated into one gradient, one all-reduce), then (--full) a
+        short untimed pass with every kernel class event-timed (the per-kernel breakdown); returns
+        (s, timing, psnr, in_sync).  `dump`: a directory that receives the last timed step's outputs
+        (dump_outputs).  Inside the timed region only the MLP kernel classes (mlp_fwd,
         mlp_bwd, wgrad: the roofline kernel is among them) are bracketed by hipEvents: each event
         pair costs the dependent launch sequence a few us (measured 1.5 % of the f32 step and 4 % of
         the f16x2 step with every kernel class timed)."""
@@ -513,8 +554,10 @@ def main():
                 dist.barrier()
             dt = time.perf_counter() - t0
             live = models[0].read_timing()
-            timing = {}
-            kb = min(5, steps) if timers_on else 0
+            if dump:  # the devices are idle: sync_all above, and read_timing synchronises
+                dump_outputs(nof, dump, models, ranks, G > 1)
+            timing = {name: v for name, v in live.items() if v[1]}  # the live (timed-region) figures
+            kb = min(5, steps) if (timers_on and a.full) else 0
             if kb:  # per-kernel breakdown: a few more steps with every kernel class timed (outside the clock)
                 # one untimed step first: read_timing synchronised, and the first timed class (pack) would
                 # otherwise measure the idle GPU waiting for the host's first launch
@@ -611,7 +654,7 @@ def main():
             "mlp_all_kernels": {"achieved": round(mlp_tf, 2), "unit": "TFLOP/s", "frac": round(mlp_tf / peak, 4)},
         }
 
-    dt, timing, psnr, in_sync = measure(a.precision)
+    dt, timing, psnr, in_sync = measure(a.precision, dump=a.dump_outputs)
     rays_per_s = B * a.steps / dt
     alts = []
     lead = rank == 0
@@ -767,7 +810,7 @@ def main():
                             "bytes_per_launch": v["bytes_per_launch"]}
                         for k, v in akernels.items() if "achieved_gbs" in v}
                 result["alt_precision"].append(entry)
-        if world == 1 and G == 1 and a.scene == "blender" and B <= 8192:
+        if not a.no_api_path and world == 1 and G == 1 and a.scene == "blender" and B <= 8192:
             result["api_path_pcie"] = api_path(torch, nof, synth, dev, B, samples, a.precision)
             result["render_1gpu"] = render_throughput(torch, nof, synth, dev, a.precision, samples=tuple(samples))
         if not a.no_integrator and world == 1 and G == 1:

@@ -19,7 +19,7 @@ def test_bench_two_ranks_rehearsal(gpu):
     env = dict(os.environ, NOF_BENCH_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "256"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "256", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -38,7 +38,7 @@ def test_bench_single_process_mode(gpu):
     """--single-process: one process drives the devices through nof_dp_init_all (grouped all-reduce);
     on the box's one GPU this is N = 1 with the 8192-ray micro-batching of a 16384-ray batch."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--single-process", "--steps", "2",
-           "--warmup", "1", "--global-batch", "16384", "--no-alt", "--no-integrator", "--no-cpu-baseline"]
+           "--warmup", "1", "--global-batch", "16384", "--full", "--no-alt", "--no-integrator", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
