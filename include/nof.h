@@ -394,6 +394,14 @@ typedef struct nof_mlp_debug {
   const float* gen_hc;    /* net_depth_condition consecutive [M][net_width_condition] (view layer first) */
 } nof_mlp_debug;
 nof_status nof_mlp_debug_view(nof_mlp* m, int32_t level, nof_mlp_debug* out);
+/* Dispatch tally of the any-shape path (tests and tooling): how many launches of each kernel variant
+ * (k_gemm / k_gemm_ws instantiations, the encoders, the slab and ray sums) this object has made since
+ * its creation or the last clear.  counts[i] belongs to nof_gen_dispatch_name(i); *n = the number of
+ * variants (min(cap, *n) counts are written), clear != 0 zeroes the tally after the read.  Host-side
+ * counters only; a fused 8x256 network launches none of these kernels and reports all zeros.
+ * nof_gen_dispatch_name: i outside [0, n) is NOF_ERR_INVALID_ARG (needs no device). */
+nof_status nof_mlp_gen_dispatch(nof_mlp* m, int32_t clear, uint32_t* counts, int32_t cap, int32_t* n);
+nof_status nof_gen_dispatch_name(int32_t i, const char** name);
 
 /* ---- AcceleratedAdamOptimizer (AcceleratedAdamOptimizer.h:5-20) ------------------------------ */
 /* ctor AcceleratedAdamOptimizer.cpp:6-21 (m, v zero-initialised: D18); cfg supplies device/stream */

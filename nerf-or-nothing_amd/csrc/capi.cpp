@@ -447,6 +447,18 @@ nof_status nof_mlp_layer_sizes(nof_mlp* m, int32_t* out, int32_t cap, int32_t* c
 nof_status nof_mlp_debug_view(nof_mlp* m, int32_t level, nof_mlp_debug* out) {
   return guard([&] { ARG(m && out); *out = M(m)->debug_view(level); });
 }
+nof_status nof_mlp_gen_dispatch(nof_mlp* m, int32_t clear, uint32_t* counts, int32_t cap, int32_t* n) {
+  return guard([&] {
+    ARG(m && n && cap >= 0 && (counts || cap == 0));
+    const uint32_t* c = M(m)->gen_dispatch();
+    for (int i = 0; i < cap && i < nof::kGvCount; ++i) counts[i] = c[i];
+    *n = nof::kGvCount;
+    if (clear) M(m)->clear_gen_dispatch();
+  });
+}
+nof_status nof_gen_dispatch_name(int32_t i, const char** name) {
+  return guard([&] { ARG(name && nof::gen_variant_name(i)); *name = nof::gen_variant_name(i); });
+}
 
 // ---- AcceleratedAdamOptimizer ---------------------------------------------------------------
 nof_status nof_adam_create(const int32_t* layer_sizes, int32_t num_layers, const nof_config* cfg, nof_adam** out) {

@@ -282,8 +282,10 @@ void AcceleratedMLP::forward_fused(int level, int n, int samples, const float* t
     GenLevel& G = gl_[level];
     tb(kTMlpFwd);
     NOF_HIP(nof::launch_cast(n, samples, t, origins, dirs, radii, G.mean.p, G.cov.p, st_, cfg_.ray_shape));
+    int v;
     NOF_HIP(nof::launch_encode_g(n, samples, G.mean.p, G.cov.p, dirs, gmin_deg_, gP_, gVd_, G.enc_pos.p, G.enc_dir.p,
-                                 st_));
+                                 st_, &v));
+    tally(v);
     te(kTMlpFwd);
     gen_forward(level, G.enc_pos.p, G.enc_dir.p);
     return;
@@ -789,10 +791,12 @@ static nof::GemmSrc gsrc(const float* p, int64_t si, int64_t sk, int idiv = 1) {
   return s;
 }
 
-static void gemm1(nof::GemmArgs a, hipStream_t st) {  // no split: one k chunk
+void AcceleratedMLP::gemm1(nof::GemmArgs a) {  // no split: one k chunk
   a.kchunk = (a.K1 + a.K2 + 15) / 16 * 16;
   a.slab_stride = 0;
-  NOF_HIP(nof::launch_gemm(a, 1, st));
+  int v;
+  NOF_HIP(nof::launch_gemm(a, 1, st_, &v));
+  tally(v);
 }
 
 // split-K of a weight gradient (k = the level's M samples, or its rays): about 1024 workgroups (four per
@@ -870,19 +874,23 @@ void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t 
   a.kchunk = kc; a.slab_stride = (int64_t)nout * ncols;
   float* bias_part = slab + (size_t)ks * nout * ncols;  // the bias gradient's per-chunk sums [ks][nout]
   if (bias_dst) a.rowsum = bias_part;
-  NOF_HIP(nof::launch_gemm(a, ks, st_));
+  int v;
+  NOF_HIP(nof::launch_gemm(a, ks, st_, &v));
+  tally(v);
   wg_jobs_.push_back({slab, dst, a.slab_stride, ld, nout, ncols, ncols, ks, accumulate});
   if (bias_dst) wg_jobs_.push_back({bias_part, bias_dst, nout, nout, 1, nout, nout, ks, accumulate});
 }
 
 bool AcceleratedMLP::gen_gemm(nof::GemmArgs a) {
   if (nof::gemm_ws_fits(a)) {
-    NOF_HIP(nof::launch_gemm_ws(a, st_));
+    int v;
+    NOF_HIP(nof::launch_gemm_ws(a, st_, &v));
+    tally(v);
     return true;
   }
   NOF_REQUIRE(!a.mask_in, "a ReLU-bit mask needs the weight-stationary kernel");
   a.mask_out = nullptr;
-  gemm1(a, st_);
+  gemm1(a);
   return false;
 }
 
@@ -969,12 +977,14 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   auto masked = [&](nof::GemmArgs a, int mlay, const float* mask, int width) {
     a.mask_in = MB(mlay);
     if (G.mb_ok[mlay] && nof::gemm_ws_fits(a)) {
-      NOF_HIP(nof::launch_gemm_ws(a, st_));
+      int v;
+      NOF_HIP(nof::launch_gemm_ws(a, st_, &v));
+      tally(v);
       return;
     }
     a.mask_in = nullptr;
     a.G = mask; a.gi = width; a.gj = 1;
-    gemm1(a, st_);
+    gemm1(a);
   };
   // dX of layer l into C, masked by the activation `mask` > 0: C[m][j] = sum_o dZ[m][o] W_l[o][j]
   auto dx = [&](const float* dzp, int64_t ldz, int nout, int l, int mlay, const float* mask, int width, float* C) {
@@ -1004,7 +1014,10 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   // view layer: columns [0, W) against h_{D-1}, [W, W + Vd) against the ray's view PE
   gen_wgrad(gr + woff_[D + 1], W + Vd, cur, Wc, Wc, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D + 1]);
   // (the view PE is per ray: dW_pe = sum over rays of (sum over the ray's samples of dZ) PE(ray))
-  if (!dry) NOF_HIP(nof::launch_ray_sum(M / S, S, Wc, cur, Wc, gray_.p, st_));
+  if (!dry) {
+    NOF_HIP(nof::launch_ray_sum(M / S, S, Wc, cur, Wc, gray_.p, st_));
+    tally(nof::kGvRaySum);
+  }
   gen_wgrad(gr + woff_[D + 1] + W, W + Vd, gray_.p, Wc, Wc, gsrc(G.ed, 1, Vd), Vd, M / S, acc);
   // density head
   gen_wgrad(gr + woff_[D], W, dz + 3, 4, 1, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D]);
@@ -1033,7 +1046,9 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     }
   }
   if (!dry) {
-    NOF_HIP(nof::launch_slab_sums(wg_jobs_.data(), (int)wg_jobs_.size(), st_));
+    int batches;
+    NOF_HIP(nof::launch_slab_sums(wg_jobs_.data(), (int)wg_jobs_.size(), st_, &batches));
+    tally(nof::kGvSlabSums, batches);
     te(kTMlpBwd);
   }
   wg_jobs_.clear();

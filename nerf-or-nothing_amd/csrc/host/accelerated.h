@@ -151,6 +151,10 @@ class AcceleratedMLP {
   hipStream_t stream() const { return st_; }
   int device() const { return cfg_.device; }
   nof_mlp_debug debug_view(int level) const;
+  // launches per nof::GenVariant of the any-shape path since construction or the last clear (host-side
+  // counts of real launches: the slab-sizing dry run is not one; all zero for the fused networks)
+  const uint32_t* gen_dispatch() const { return disp_; }
+  void clear_gen_dispatch() { for (uint32_t& c : disp_) c = 0; }
   // non-finite flags: [0] forward (set by the owner's integrator), [1] output gradients (f16x2 scaling)
   uint32_t* numeric_flags() const { return numeric_.p; }
   // The fused step's integrator adjoint takes a level's delta-scale maximum (f16 modes) from the values
@@ -221,6 +225,9 @@ class AcceleratedMLP {
   // an unsplit product: the weight-stationary kernel where the shape fits it (gemm_ws.hip), else k_gemm;
   // returns whether the weight-stationary kernel ran
   bool gen_gemm(nof::GemmArgs a);
+  void gemm1(nof::GemmArgs a);  // k_gemm, no split: one k chunk
+  uint32_t disp_[nof::kGvCount] = {};
+  void tally(int variant, int launches = 1) { if (variant >= 0) disp_[variant] += (uint32_t)launches; }
   std::vector<GenLevel> gl_;
   DevBuf<float> gd0_, gd1_, gdz_, gslab_;  // dZ ping-pong [M][max(W, Wc)], heads dz [M][4], split-K partials
   DevBuf<float> gray_;                    // per-ray sums of the view layer's dZ [rays][Wc]

@@ -231,7 +231,8 @@ bool gemm_ws_fits(const GemmArgs& a) {
          a.cj == 1 && (!a.mask_out || a.relu);
 }
 
-hipError_t launch_gemm_ws(const GemmArgs& a, hipStream_t st) {
+hipError_t launch_gemm_ws(const GemmArgs& a, hipStream_t st, int* variant) {
+  if (variant) *variant = -1;
   if (!gemm_ws_fits(a)) return hipErrorInvalidValue;
   const int nit = (a.M + kWsRows - 1) / kWsRows;
   const dim3 grid(std::min(nit, device_cus()));  // persistent: one workgroup per CU
@@ -239,27 +240,30 @@ hipError_t launch_gemm_ws(const GemmArgs& a, hipStream_t st) {
   // layer 0, layers 1..3 and the dX products, the heads, the view layer, the view layer's dX
   const int NT = (a.N + 15) / 16, C1 = (a.K1 + 15) / 16, C2 = (a.K2 + 15) / 16;
   const bool v2 = a.K2 > 0 && ws_vec(a.A2, a.K2);
-  if (a.K1 == 16 * C1) {
-    if (NT == 8 && C1 == 6 && C2 == 0) { hipLaunchKernelGGL((k_gemm_ws<8, 6, 0, false>), grid, dim3(kWsThreads), 0, st, a); return hipGetLastError(); }
-    if (NT == 8 && C1 == 8 && C2 == 0) { hipLaunchKernelGGL((k_gemm_ws<8, 8, 0, false>), grid, dim3(kWsThreads), 0, st, a); return hipGetLastError(); }
-    if (NT == 1 && C1 == 8 && C2 == 0) { hipLaunchKernelGGL((k_gemm_ws<1, 8, 0, false>), grid, dim3(kWsThreads), 0, st, a); return hipGetLastError(); }
-    if (NT == 8 && C1 == 8 && C2 == 2 && !v2) { hipLaunchKernelGGL((k_gemm_ws<8, 8, 2, false>), grid, dim3(kWsThreads), 0, st, a); return hipGetLastError(); }
-    if (NT == 8 && C1 == 8 && C2 == 1 && !v2) { hipLaunchKernelGGL((k_gemm_ws<8, 8, 1, false>), grid, dim3(kWsThreads), 0, st, a); return hipGetLastError(); }
-  } else if (NT == 8 && C1 == 1 && C2 == 0) {  // the RGB head's dX (K1 = 3)
-    hipLaunchKernelGGL((k_gemm_ws<8, 1, 0, false, true>), grid, dim3(kWsThreads), 0, st, a);
+  auto go = [&](auto kern, int v) {
+    if (variant) *variant = v;
+    hipLaunchKernelGGL(kern, grid, dim3(kWsThreads), 0, st, a);
     return hipGetLastError();
+  };
+  if (a.K1 == 16 * C1) {
+    if (NT == 8 && C1 == 6 && C2 == 0) return go(k_gemm_ws<8, 6, 0, false>, kGvWs_8_6_0);
+    if (NT == 8 && C1 == 8 && C2 == 0) return go(k_gemm_ws<8, 8, 0, false>, kGvWs_8_8_0);
+    if (NT == 1 && C1 == 8 && C2 == 0) return go(k_gemm_ws<1, 8, 0, false>, kGvWs_1_8_0);
+    if (NT == 8 && C1 == 8 && C2 == 2 && !v2) return go(k_gemm_ws<8, 8, 2, false>, kGvWs_8_8_2);
+    if (NT == 8 && C1 == 8 && C2 == 1 && !v2) return go(k_gemm_ws<8, 8, 1, false>, kGvWs_8_8_1);
+  } else if (NT == 8 && C1 == 1 && C2 == 0) {  // the RGB head's dX (K1 = 3)
+    return go(k_gemm_ws<8, 1, 0, false, true>, kGvWs_8_1_0_T1);
   }
   switch ((a.N + 15) / 16) {
-    case 1: hipLaunchKernelGGL(k_gemm_ws<1>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(k_gemm_ws<2>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(k_gemm_ws<3>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(k_gemm_ws<4>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 5: hipLaunchKernelGGL(k_gemm_ws<5>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 6: hipLaunchKernelGGL(k_gemm_ws<6>, grid, dim3(kWsThreads), 0, st, a); break;
-    case 7: hipLaunchKernelGGL(k_gemm_ws<7>, grid, dim3(kWsThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(k_gemm_ws<8>, grid, dim3(kWsThreads), 0, st, a); break;
+    case 1: return go(k_gemm_ws<1>, kGvWsRuntime + 0);
+    case 2: return go(k_gemm_ws<2>, kGvWsRuntime + 1);
+    case 3: return go(k_gemm_ws<3>, kGvWsRuntime + 2);
+    case 4: return go(k_gemm_ws<4>, kGvWsRuntime + 3);
+    case 5: return go(k_gemm_ws<5>, kGvWsRuntime + 4);
+    case 6: return go(k_gemm_ws<6>, kGvWsRuntime + 5);
+    case 7: return go(k_gemm_ws<7>, kGvWsRuntime + 6);
+    default: return go(k_gemm_ws<8>, kGvWsRuntime + 7);
   }
-  return hipGetLastError();
 }
 
 }  // namespace nof

@@ -383,7 +383,20 @@ __global__ void k_heads_bwd(int M, const float* __restrict__ dsigma, const float
   }
 }
 
-hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st) {
+const char* gen_variant_name(int v) {
+  static const char* const kNames[kGvCount] = {
+      "k_gemm<64,false,false>.unsplit", "k_gemm<64,true,false>.unsplit", "k_gemm<64,false,true>.unsplit",
+      "k_gemm<64,true,true>.unsplit", "k_gemm<64,false,false>.splitk", "k_gemm<64,true,false>.splitk",
+      "k_gemm<64,false,true>.splitk", "k_gemm<64,true,true>.splitk", "k_gemm<128,false,false>.splitk",
+      "k_gemm<128,true,false>.splitk", "k_gemm_ws<8,6,0,false>", "k_gemm_ws<8,8,0,false>", "k_gemm_ws<1,8,0,false>",
+      "k_gemm_ws<8,8,2,false>", "k_gemm_ws<8,8,1,false>", "k_gemm_ws<8,1,0,false,true>", "k_gemm_ws<1>",
+      "k_gemm_ws<2>", "k_gemm_ws<3>", "k_gemm_ws<4>", "k_gemm_ws<5>", "k_gemm_ws<6>", "k_gemm_ws<7>", "k_gemm_ws<8>",
+      "k_encode_g", "k_encode_g4", "k_slab_sums", "k_ray_sum"};
+  return v >= 0 && v < kGvCount ? kNames[v] : nullptr;
+}
+
+hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st, int* variant) {
+  if (variant) *variant = -1;
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   if (ksplit < 1 || a.kchunk <= 0 || a.kchunk % kGK != 0 || !a.A1.p || !a.B1.p || (a.K2 > 0 && (!a.A2.p || !a.B2.p)) ||
       a.A1.idiv < 1 || a.A2.idiv < 1 || a.B1.idiv < 1 || a.B2.idiv < 1)
@@ -400,27 +413,33 @@ hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st) {
   if (tiles > 0x7fffffff || ksplit > 65535) return hipErrorInvalidValue;
   const dim3 grid((unsigned)tiles, 1, ksplit);
   const bool two = a.K2 > 0;
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kGThreads), 0, st, a); };
+  auto go = [&](auto kern, int v) {
+    if (variant) *variant = v;
+    hipLaunchKernelGGL(kern, grid, dim3(kGThreads), 0, st, a);
+  };
   const bool mask = a.G != nullptr;
+  const int v64 = ksplit > 1 ? kGvGemm64Split : kGvGemm64;
   if (two) {
-    if (wide) go(k_gemm<128, true, false>);
-    else if (mask) go(k_gemm<64, true, true>);
-    else go(k_gemm<64, true, false>);
+    if (wide) go(k_gemm<128, true, false>, kGvGemm128Split + 1);
+    else if (mask) go(k_gemm<64, true, true>, v64 + 3);
+    else go(k_gemm<64, true, false>, v64 + 1);
   } else {
-    if (wide) go(k_gemm<128, false, false>);
-    else if (mask) go(k_gemm<64, false, true>);
-    else go(k_gemm<64, false, false>);
+    if (wide) go(k_gemm<128, false, false>, kGvGemm128Split);
+    else if (mask) go(k_gemm<64, false, true>, v64 + 2);
+    else go(k_gemm<64, false, false>, v64);
   }
   return hipGetLastError();
 }
-hipError_t launch_slab_sums(const SlabJob* jobs, int n, hipStream_t st) {
+hipError_t launch_slab_sums(const SlabJob* jobs, int n, hipStream_t st, int* launches) {
   SlabBatch b{};
   int blocks = 0;
+  if (launches) *launches = 0;
   for (int i = 0; i <= n; ++i) {
     if (i == n || b.n == kSlabJobsMax) {  // flush
       if (b.n) {
         for (int k = b.n; k <= kSlabJobsMax; ++k) b.first[k] = blocks;
         hipLaunchKernelGGL(k_slab_sums, dim3((unsigned)blocks), dim3(256), 0, st, b);
+        if (launches) ++*launches;
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
       }
@@ -457,16 +476,19 @@ hipError_t launch_ray_sum(int R, int S, int cols, const float* in, int64_t ld, f
   return hipGetLastError();
 }
 hipError_t launch_encode_g(int n, int S, const float* mean, const float* cov, const float* d, int min_deg, int P, int Vd,
-                           float* enc_pos, float* enc_dir, hipStream_t st) {
+                           float* enc_pos, float* enc_dir, hipStream_t st, int* variant) {
+  if (variant) *variant = -1;
   if (P % 4 == 0 && ((uintptr_t)enc_pos & 15) == 0) {
     const int64_t total = std::max((int64_t)n * S * (P / 4), (int64_t)n * Vd);
     if (total <= 0) return hipSuccess;
+    if (variant) *variant = kGvEncode4;
     hipLaunchKernelGGL(k_encode_g4, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, S, mean, cov, d, min_deg,
                        P, Vd, enc_pos, enc_dir);
     return hipGetLastError();
   }
   const int64_t total = std::max((int64_t)n * S * P, (int64_t)n * Vd);
   if (total <= 0) return hipSuccess;
+  if (variant) *variant = kGvEncode;
   hipLaunchKernelGGL(k_encode_g, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, S, mean, cov, d, min_deg,
                      P, Vd, enc_pos, enc_dir);
   return hipGetLastError();

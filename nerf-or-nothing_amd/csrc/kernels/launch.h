@@ -204,11 +204,32 @@ struct GemmArgs {
   const uint32_t* mask_in = nullptr;
   uint32_t* mask_out = nullptr;
 };
-hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st);
+// Every kernel variant the any-shape launchers can select (AcceleratedMLP's dispatch tally: tests and
+// tooling see which instantiation a product ran on).  A launcher reports its pick through its optional
+// `variant` out-parameter, set where the template is chosen (-1: nothing launched).
+enum GenVariant : int {
+  kGvGemm64 = 0,        // k_gemm<64, TWO, MASK>, one k chunk: + TWO + 2 MASK
+  kGvGemm64Split = 4,   // ... split-K (ksplit > 1): + TWO + 2 MASK
+  kGvGemm128Split = 8,  // k_gemm<128, TWO, false> (split-K only): + TWO
+  kGvWs_8_6_0 = 10,     // k_gemm_ws's static chunk shapes <NT, SC1, SC2, SV2[, T1]>
+  kGvWs_8_8_0,
+  kGvWs_1_8_0,
+  kGvWs_8_8_2,
+  kGvWs_8_8_1,
+  kGvWs_8_1_0_T1,
+  kGvWsRuntime = 16,    // k_gemm_ws<NT>, runtime chunk shape: + NT - 1 (NT = 1 .. 8)
+  kGvEncode = 24,       // k_encode_g
+  kGvEncode4,           // k_encode_g4
+  kGvSlabSums,          // k_slab_sums (one count per batch launched)
+  kGvRaySum,            // k_ray_sum
+  kGvCount
+};
+const char* gen_variant_name(int v);  // null outside [0, kGvCount)
+hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st, int* variant = nullptr);
 // gemm_ws.hip: the weight-stationary form for N <= 128, 16-padded K1 + K2 <= 160, no split, no G / rowsum
 constexpr int kWsMaxN = 128, kWsMaxK = 160;
 bool gemm_ws_fits(const GemmArgs& a);
-hipError_t launch_gemm_ws(const GemmArgs& a, hipStream_t st);
+hipError_t launch_gemm_ws(const GemmArgs& a, hipStream_t st, int* variant = nullptr);
 // dst[r ld + c] (+)= sum_{z < nz} slabs[z stride + r pitch + c] (a fixed order), r < rows, c < cols
 hipError_t launch_slab_sum(int rows, int cols, int pitch, int nz, const float* slabs, int64_t stride, float* dst,
                            int64_t ld, int accumulate, hipStream_t st);
@@ -226,12 +247,12 @@ struct SlabBatch {
   int first[kSlabJobsMax + 1];
   int n;
 };
-hipError_t launch_slab_sums(const SlabJob* jobs, int n, hipStream_t st);
+hipError_t launch_slab_sums(const SlabJob* jobs, int n, hipStream_t st, int* launches = nullptr);  // (batches launched)
 // IPE at degrees [min_deg, min_deg + P / 6) per sample, view PE (Vd = 3 + 6 deg_view features) per ray
 // out[r][c] = sum over a ray's S sample rows of in (the per-ray operand's weight gradient over rays)
 hipError_t launch_ray_sum(int R, int S, int cols, const float* in, int64_t ld, float* out, hipStream_t st);
 hipError_t launch_encode_g(int n, int S, const float* mean, const float* cov, const float* d, int min_deg, int P,
-                           int Vd, float* enc_pos, float* enc_dir, hipStream_t st);
+                           int Vd, float* enc_pos, float* enc_dir, hipStream_t st, int* variant = nullptr);
 // z [M][4] (density, rgb pre-activations) -> sigma [M], rgb [M][3]; backward: dz [M][4]
 hipError_t launch_heads_fwd(int M, const float* z, float* sigma, float* rgb, float dbias, float rgb_scale,
                             float rgb_pad, hipStream_t st);

@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     device_checks_selftest,
     device_count,
     device_tensor,
+    gen_dispatch_names,
     generate_rays,
     grad_bucket_spans,
     image_metrics,

@@ -139,6 +139,8 @@ SIGNATURES = {
     "nof_mlp_flat_grads": [P, C.POINTER(P), C.POINTER(C.c_int64)],
     "nof_mlp_layer_sizes": [P, C.POINTER(I32), I32, C.POINTER(I32)],
     "nof_mlp_debug_view": [P, I32, C.POINTER(nof_mlp_debug)],
+    "nof_mlp_gen_dispatch": [P, I32, C.POINTER(U32), I32, C.POINTER(I32)],
+    "nof_gen_dispatch_name": [I32, C.POINTER(C.c_char_p)],
     "nof_adam_create": [C.POINTER(I32), I32, C.POINTER(nof_config), C.POINTER(P)],
     "nof_adam_step": [P, PP, PP, F],
     "nof_adam_iteration": [P, C.POINTER(I32)],

@@ -54,6 +54,14 @@ def _ptr_list(pp, count) -> list[int]:
     return [C.cast(pp[i], C.c_void_p).value or 0 for i in range(count)]
 
 
+def gen_dispatch_names() -> list[str]:
+    """The any-shape path's kernel variants in the order of the dispatch tally (host only, no GPU)."""
+    out, name = [], C.c_char_p()
+    while lib().nof_gen_dispatch_name(len(out), C.byref(name)) == 0:
+        out.append(name.value.decode())
+    return out
+
+
 class AcceleratedMLP:
     """Borrowed view of the MLP owned by an AcceleratedMipNeRF (AcceleratedMLP.h:7-45)."""
 
@@ -104,6 +112,17 @@ class AcceleratedMLP:
         call("nof_mlp_debug_view", self._h, level, C.byref(d))
         return {k: getattr(d, k) for k in ("M", "act_in", "act_h", "act_h9", "masks", "zhead", "delta", "delta9x",
                                            "generic", "gen_h", "gen_hc")}
+
+    def gen_dispatch(self, clear: bool = False) -> dict:
+        """Launches per kernel variant of the any-shape path since creation or the last clear
+        (name -> count, every variant listed; all zero for a fused network)."""
+        names = gen_dispatch_names()
+        counts = (C.c_uint32 * len(names))()
+        n = C.c_int32()
+        call("nof_mlp_gen_dispatch", self._h, int(bool(clear)), counts, len(names), C.byref(n))
+        if n.value != len(names):
+            raise RuntimeError(f"nof_mlp_gen_dispatch: {n.value} variants, {len(names)} names")
+        return {k: int(counts[i]) for i, k in enumerate(names)}
 
     def relu_masks(self, level: int) -> np.ndarray:
         """Decode the forward's packed ReLU bits -> uint8 [M, 8*256 + 128] (h0..h7, h9); any-shape

@@ -77,6 +77,31 @@ def test_null_arguments_rejected():
     assert b"invalid argument" in nof.lib().nof_last_error()
 
 
+def test_gen_dispatch_name_list():
+    """The any-shape dispatch tally's name table through ctypes (host only): one distinct name per variant
+    (the ten k_gemm picks of launch_gemm, k_gemm_ws's six static and eight runtime shapes, both encoders,
+    the slab and ray sums), a status past either end, null arguments refused."""
+    import nof
+
+    lib = nof.lib()
+    names, name = [], C.c_char_p()
+    while lib.nof_gen_dispatch_name(len(names), C.byref(name)) == 0:
+        names.append(name.value.decode())
+        assert len(names) <= 256
+    assert names == nof.gen_dispatch_names()
+    assert len(names) == len(set(names)) == 28
+    assert sum(n.startswith("k_gemm<") for n in names) == 10
+    assert sum(n.startswith("k_gemm_ws<") for n in names) == 14
+    assert {f"k_gemm_ws<{nt}>" for nt in range(1, 9)} <= set(names)
+    assert {"k_encode_g", "k_encode_g4", "k_slab_sums", "k_ray_sum"} <= set(names)
+    assert lib.nof_gen_dispatch_name(len(names), C.byref(name)) == 1
+    assert lib.nof_gen_dispatch_name(-1, C.byref(name)) == 1
+    assert lib.nof_gen_dispatch_name(0, None) == 1
+    n = C.c_int32()
+    assert lib.nof_mlp_gen_dispatch(None, 0, None, 0, C.byref(n)) == 1
+    assert hasattr(nof.AcceleratedMLP, "gen_dispatch")
+
+
 def test_python_mirror_names():
     import nof
 

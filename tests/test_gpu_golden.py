@@ -85,4 +85,8 @@ def test_hip_step_matches_golden_fixture(gpu, precision):
     print(f"precision {precision}: sampled gradients rel L2 {e:.2e}, outside layer 0 {e_rest:.2e}; norms worst "
           f"{float(np.max(rel)):.2e}")
     assert e_rest < (5e-3 if precision == 4 else GRAD_TOLS[precision]), f"sampled gradient entries: rel L2 {e_rest:.3g}"
+    if precision == 4:  # layer 0's sampled entries (W0 / b0): loosely, so they are not left unbounded (measured 3.2e-2)
+        e_l0 = rel_l2(G[idx[~rest]], g["grad_vals"][~rest])
+        print(f"precision {precision}: layer-0 sampled gradients ({int(np.sum(~rest))} entries) rel L2 {e_l0:.2e}")
+        assert np.any(~rest) and e_l0 < 5e-2, f"layer-0 sampled gradient entries: rel L2 {e_l0:.3g}"
     model.close()
