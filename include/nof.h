@@ -410,6 +410,34 @@ nof_status nof_adam_create(const int32_t* layer_sizes, int32_t num_layers, const
 nof_status nof_adam_step(nof_adam* a, float* const* params, float* const* grads, float learning_rate);
 nof_status nof_adam_iteration(nof_adam* a, int32_t* iteration);
 nof_status nof_adam_destroy(nof_adam* a);
+/* The training options the reference declares but never implements (Config.GradMaxNorm, Config.GradMaxVal,
+ * TrainState.cs:58-59; Config.WeightDecayMult, TrainState.cs:70) and its statistics record (StatsUtil.cs:13,16-18,
+ * which Program.LossFn fills with weightL2 = 0 alone, Program.cs:82-87), with mip-NeRF's meaning.  All in fp32,
+ * element-wise over all P parameters (biases included), g = the gradient handed to nof_adam_step (data parallel:
+ * the all-reduced one), p = the parameters before the update:
+ *   g1 = g + ((2 weight_decay_mult) / P) p      (the loss term weight_decay_mult * sum p^2 / P; g when 0)
+ *   g2 = clamp(g1, -grad_max_val, grad_max_val) (g1 when grad_max_val == 0)
+ *   clip_scale = min(1, grad_max_norm / (1e-7 + |g2|))  (1 when grad_max_norm == 0);  Adam is fed g2 clip_scale
+ * weight_l2 = sum p^2 / P, grad_norm = |g1|, grad_abs_max = max |g1|, grad_norm_clipped = clip_scale |g2|.  The
+ * norms are global over all tensors and a pure function of the inputs (fixed summation order, no float atomics):
+ * bit-identical run to run and replica to replica.  A step with any option set (stats != 0 gathers the record
+ * alone) costs one launch more than the plain step, no host synchronisation and no allocation.  With every
+ * option 0 (the default) the step is the plain one.  Options are hyper-parameters, not state: checkpoints do not
+ * hold them.  Negative or NaN options are NOF_ERR_INVALID_ARG. */
+typedef struct nof_step_stats {
+  float weight_l2, grad_norm, grad_abs_max, grad_norm_clipped, clip_scale;
+  int32_t iteration; /* the Adam step (nof_adam_iteration) the record belongs to */
+} nof_step_stats;
+nof_status nof_adam_set_options(nof_adam* a, float grad_max_norm, float grad_max_val, float weight_decay_mult,
+                                int32_t stats);
+nof_status nof_adam_get_options(nof_adam* a, float* grad_max_norm, float* grad_max_val, float* weight_decay_mult,
+                                int32_t* stats);
+/* Synchronises the optimizer's stream and returns the last step's record; NOF_ERR_INVALID_ARG when no step has
+ * gathered statistics yet. */
+nof_status nof_adam_stats(nof_adam* a, nof_step_stats* out);
+/* The optimizer's moments (device memory, borrowed; *count floats each, in the order of the layer sizes): what a
+ * checkpoint stores of it, for tests and tooling.  Work on the optimizer's stream may still be writing them. */
+nof_status nof_adam_moments(nof_adam* a, float** m, float** v, int64_t* count);
 
 /* ---- AcceleratedGradientCalculator (AcceleratedGradientCalculator.h:8-17) -------------------- */
 nof_status nof_gradcalc_create(int32_t batch_size, const nof_config* cfg, nof_gradcalc** out);

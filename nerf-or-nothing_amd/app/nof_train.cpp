@@ -22,7 +22,11 @@
 //   nof_train --records train_data.bin [--steps K] [--batch N] [--precision f32|split|f16x2|f16split|f16]
 //             [--print-every P] [--save-every S --ckpt-dir DIR] [--resume CKPT] [--host-api]
 //             [--seed X] [--device D | --gpus N [--dp rccl|loopback] [--attach]] [--micro-batch M]
-//             [--dump-params FILE]
+//             [--dump-params FILE] [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]
+//
+// --grad-max-norm / --grad-max-val / --weight-decay: Config.GradMaxNorm, GradMaxVal, WeightDecayMult
+// (TrainState.cs:58-59,70; declared by the reference, implemented here: nof_adam_set_options).  With any of them,
+// or --stats, every print line carries the optimizer's record (StatsUtil.cs:13,16-18) after the loss.
 //
 // --gpus N: data parallelism in ONE process over devices 0..N-1 (SURVEY 8e's process model): the
 // global batch of --batch rays is sharded into N contiguous shards with global ray ids (every shard
@@ -65,6 +69,9 @@ struct Args {
   // Config (TrainState.cs:54-58)
   float lr_init = 5e-4f, lr_final = 5e-6f, lr_delay_mult = 0.01f;
   int max_steps = 1000000, lr_delay_steps = 2500;
+  // Config.GradMaxNorm, GradMaxVal (TrainState.cs:58-59), WeightDecayMult (TrainState.cs:70): 0 = off
+  float grad_max_norm = 0.0f, grad_max_val = 0.0f, weight_decay = 0.0f;
+  bool stats = false;  // print the step statistics even with every option off
 };
 
 [[noreturn]] void usage(int code) {
@@ -76,7 +83,8 @@ struct Args {
                "                 [--net-depth D] [--net-width W] [--net-depth-condition DC] [--net-width-condition WC]\n"
                "                 [--samples S0,S1[,...]]  (e.g. BASELINE configs[0]: --net-depth 4 --net-width 128 "
                "--samples 64,64)\n"
-               "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n");
+               "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n"
+               "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n");
   std::exit(code);
 }
 
@@ -108,6 +116,10 @@ Args parse(int argc, char** argv) {
     else if (k == "--cylinder") a.cylinder = true;
     else if (k == "--density-bias") a.density_bias = std::strtof(val(), nullptr);
     else if (k == "--rgb-padding") a.rgb_padding = std::strtof(val(), nullptr);
+    else if (k == "--grad-max-norm") a.grad_max_norm = std::strtof(val(), nullptr);
+    else if (k == "--grad-max-val") a.grad_max_val = std::strtof(val(), nullptr);
+    else if (k == "--weight-decay") a.weight_decay = std::strtof(val(), nullptr);
+    else if (k == "--stats") a.stats = true;
     else if (k == "--net-depth") a.net_depth = std::atoi(val());
     else if (k == "--net-width") a.net_width = std::atoi(val());
     else if (k == "--net-depth-condition") a.net_depth_condition = std::atoi(val());
@@ -225,6 +237,7 @@ int main(int argc, char** argv) {
   const int G = a.gpus > 0 ? a.gpus : 1;
   const int shard = a.batch / G;
   const int micro = a.micro > 0 ? a.micro : shard;
+  const bool with_stats = a.stats || a.grad_max_norm != 0.0f || a.grad_max_val != 0.0f || a.weight_decay != 0.0f;
   std::vector<Replica> rs(G);
   for (int r = 0; r < G; ++r) {
     Replica& R = rs[r];
@@ -258,6 +271,8 @@ int main(int argc, char** argv) {
     int32_t sizes[64], nsizes = 0;
     CHECK(nof_mipnerf_layer_sizes(R.model, sizes, 64, &nsizes));
     CHECK(nof_adam_create(sizes, nsizes, &R.cfg, &R.adam));
+    if (with_stats)  // hyper-parameters, not checkpoint state: passed again on --resume
+      CHECK(nof_adam_set_options(R.adam, a.grad_max_norm, a.grad_max_val, a.weight_decay, a.stats ? 1 : 0));
     if (a.host_api) CHECK(nof_gradcalc_create(shard, &R.cfg, &R.calc));
     CHECK(nof_mipnerf_mlp(R.model, &R.mlp));
     CHECK(nof_mlp_params(R.mlp, &R.params));  // model.mlp.allParams
@@ -356,7 +371,14 @@ int main(int argc, char** argv) {
         num += (double)l * m;
         den += m;
       }
-      std::printf("Step %d/%d, Loss: %.9g\n", step, a.max_steps, G == 1 ? (double)loss1 : num / den);
+      std::printf("Step %d/%d, Loss: %.9g", step, a.max_steps, G == 1 ? (double)loss1 : num / den);
+      if (with_stats) {  // of the all-reduced gradient: the same record on every replica
+        nof_step_stats st;
+        CHECK(nof_adam_stats(rs[0].adam, &st));
+        std::printf(", grad_norm: %.9g, grad_abs_max: %.9g, grad_norm_clipped: %.9g, weight_l2: %.9g",
+                    (double)st.grad_norm, (double)st.grad_abs_max, (double)st.grad_norm_clipped, (double)st.weight_l2);
+      }
+      std::printf("\n");
       std::fflush(stdout);
     }
     if (a.save_every && step % a.save_every == 0) {

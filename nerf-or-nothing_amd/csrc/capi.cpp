@@ -479,6 +479,30 @@ nof_status nof_adam_step(nof_adam* a, float* const* params, float* const* grads,
 nof_status nof_adam_iteration(nof_adam* a, int32_t* it) {
   return guard([&] { ARG(a && it); *it = a->impl->iteration(); });
 }
+nof_status nof_adam_set_options(nof_adam* a, float grad_max_norm, float grad_max_val, float weight_decay_mult,
+                                int32_t stats) {
+  return guard([&] { ARG(a); a->impl->set_options(grad_max_norm, grad_max_val, weight_decay_mult, stats != 0); });
+}
+nof_status nof_adam_get_options(nof_adam* a, float* grad_max_norm, float* grad_max_val, float* weight_decay_mult,
+                                int32_t* stats) {
+  return guard([&] {
+    ARG(a);
+    bool s = false;
+    a->impl->get_options(grad_max_norm, grad_max_val, weight_decay_mult, &s);
+    if (stats) *stats = s ? 1 : 0;
+  });
+}
+nof_status nof_adam_stats(nof_adam* a, nof_step_stats* out) {
+  return guard([&] { ARG(a && out); DEV(a); *out = a->impl->stats(); });
+}
+nof_status nof_adam_moments(nof_adam* a, float** m, float** v, int64_t* count) {
+  return guard([&] {
+    ARG(a && m && v && count);
+    *m = a->impl->m();
+    *v = a->impl->v();
+    *count = a->impl->size();
+  });
+}
 nof_status nof_adam_destroy(nof_adam* a) {
   return guard([&] {
     if (!a) return;

@@ -1285,24 +1285,84 @@ AcceleratedAdamOptimizer::AcceleratedAdamOptimizer(const std::vector<int>& layer
   v_.alloc(total_);
   NOF_HIP(hipMemset(m_.p, 0, total_ * sizeof(float)));  // D18: the reference never zeroes m, v
   NOF_HIP(hipMemset(v_.p, 0, total_ * sizeof(float)));
+  partials_.alloc(4 * (size_t)nof::kAdamStatBlocks);  // the options' scratch, once: a step allocates nothing
+  record_.alloc(1);
 }
 
 void AcceleratedAdamOptimizer::step(float* const* params, float* const* grads, float lr) {
   NOF_REQUIRE(params && grads, "null params/grads");
   TraceRange r("nof:adam");
+  bool flat = true;
+  for (size_t i = 0; i < sizes_.size(); ++i)
+    flat = flat && params[i] == params[0] + off_[i] && grads[i] == grads[0] + off_[i];
+  const bool opts = gathers() && total_ > 0;
+  NOF_REQUIRE(!opts || flat || (int)sizes_.size() <= nof::kAdamMaxSegs,  // refused before the step counts
+              "Adam's options take separately allocated tensors up to 64 of them: pass views of flat arenas");
   ++iteration_;
   // host-side bias corrections exactly as AcceleratedAdamOptimizer.cpp:26-28
   const float inv1 = 1.0f / (1.0f - std::pow(0.9f, (float)iteration_));
   const float inv2 = 1.0f / (1.0f - std::pow(0.999f, (float)iteration_));
-  bool flat = true;
-  for (size_t i = 0; i < sizes_.size(); ++i)
-    flat = flat && params[i] == params[0] + off_[i] && grads[i] == grads[0] + off_[i];
-  if (flat) {
+  if (opts) {
+    // the statistics pass, then the update with the decay and the clips: one launch more than the plain step,
+    // both on st_ (in a data-parallel step st_ already waits for the last all-reduce), no host synchronisation.
+    // The norm is global: separate tensors are the segments of one virtual arena, not one launch each.
+    nof::AdamSegs s;
+    if (flat) {
+      s.n = 1;
+      s.off[1] = total_;
+      s.p[0] = params[0];
+      s.g[0] = grads[0];
+    } else {
+      s.n = (int)sizes_.size();
+      for (int i = 0; i < s.n; ++i) {
+        s.off[i] = off_[i];
+        s.p[i] = params[i];
+        s.g[i] = grads[i];
+      }
+      s.off[s.n] = total_;
+    }
+    nof::AdamOpts o;
+    o.grad_max_norm = gmn_;
+    o.grad_max_val = gmv_;
+    o.wdc = (2.0f * wd_) / (float)total_;
+    static_assert(sizeof(nof::AdamStepStats) == sizeof(nof_step_stats), "the device record is nof_step_stats");
+    NOF_HIP(nof::launch_adam_stats(total_, s, o, partials_.p, st_));
+    NOF_HIP(nof::launch_adam_opt(total_, s, m_.p, v_.p, lr, inv1, inv2, o, gmn_ > 0.0f || gmv_ > 0.0f || wd_ > 0.0f,
+                                 partials_.p, reinterpret_cast<nof::AdamStepStats*>(record_.p), iteration_, st_));
+    gathered_ = true;
+  } else if (flat) {
     NOF_HIP(nof::launch_adam(total_, params[0], grads[0], m_.p, v_.p, lr, inv1, inv2, st_));
   } else {
     for (size_t i = 0; i < sizes_.size(); ++i)
       NOF_HIP(nof::launch_adam(sizes_[i], params[i], grads[i], m_.p + off_[i], v_.p + off_[i], lr, inv1, inv2, st_));
   }
+}
+
+void AcceleratedAdamOptimizer::set_options(float grad_max_norm, float grad_max_val, float weight_decay_mult,
+                                           bool stats) {
+  // x >= 0 is false for a NaN too
+  NOF_REQUIRE(grad_max_norm >= 0.0f && grad_max_val >= 0.0f && weight_decay_mult >= 0.0f,
+              "Adam options must be >= 0 (0 = off)");
+  gmn_ = grad_max_norm;
+  gmv_ = grad_max_val;
+  wd_ = weight_decay_mult;
+  stats_ = stats;
+}
+
+void AcceleratedAdamOptimizer::get_options(float* grad_max_norm, float* grad_max_val, float* weight_decay_mult,
+                                           bool* stats) const {
+  if (grad_max_norm) *grad_max_norm = gmn_;
+  if (grad_max_val) *grad_max_val = gmv_;
+  if (weight_decay_mult) *weight_decay_mult = wd_;
+  if (stats) *stats = stats_;
+}
+
+nof_step_stats AcceleratedAdamOptimizer::stats() {
+  NOF_REQUIRE(gathered_, "no step has gathered statistics yet (nof_adam_set_options, then nof_adam_step)");
+  nof_step_stats out;
+  NOF_HIP(hipStreamSynchronize(st_));
+  NOF_HIP(hipMemcpy(&out, record_.p, sizeof(out), hipMemcpyDeviceToHost));
+  return out;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -331,8 +331,14 @@ class AcceleratedAdamOptimizer {
   void set_iteration(int it) { iteration_ = it; }
   hipStream_t stream() const { return st_; }
   int device() const { return device_; }
+  // gradient clipping, weight decay and the step statistics (include/nof.h nof_adam_set_options); hyper-parameters,
+  // not state: a checkpoint does not hold them
+  void set_options(float grad_max_norm, float grad_max_val, float weight_decay_mult, bool stats);
+  void get_options(float* grad_max_norm, float* grad_max_val, float* weight_decay_mult, bool* stats) const;
+  nof_step_stats stats();  // synchronises the stream; the last step's record
 
  private:
+  bool gathers() const { return stats_ || gmn_ > 0.0f || gmv_ > 0.0f || wd_ > 0.0f; }
   int device_ = 0;
   std::vector<int> sizes_;
   std::vector<int64_t> off_;
@@ -340,6 +346,10 @@ class AcceleratedAdamOptimizer {
   int iteration_ = 0;
   hipStream_t st_;
   DevBuf<float> m_, v_;
+  float gmn_ = 0.0f, gmv_ = 0.0f, wd_ = 0.0f;
+  bool stats_ = false, gathered_ = false;
+  DevBuf<double> partials_;        // the statistics pass's per-block partials (launch.h), allocated once
+  DevBuf<nof_step_stats> record_;  // written by the update launch
 };
 
 // ---------------------------------------------------------------------------------------------

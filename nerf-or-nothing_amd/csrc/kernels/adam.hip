@@ -40,6 +40,142 @@ hipError_t launch_adam(int64_t n, float* p, const float* g, float* m, float* v, 
   return hipGetLastError();
 }
 
+// ---- Adam's options: weight decay, gradient clipping, step statistics (launch.h, include/nof.h) ----
+// The options the reference declares and never implements (Config.GradMaxNorm / GradMaxVal, TrainState.cs:58-59;
+// Config.WeightDecayMult, TrainState.cs:70) with mip-NeRF's meaning, and the record of StatsUtil.cs:13,16-18.
+// Two launches: k_adam_stats leaves per-block partial sums, k_adam_opt sums them again in every block that needs
+// the clip scale (the launch boundary is the only hand-off between blocks) and then runs k_adam's update.  Every
+// sum has a fixed order: a thread's grid-stride elements in index order, the wave64 butterfly, the block's four
+// waves in wave order, the partials by the same butterfly (partial b in thread b).  No float atomics: the
+// statistics and the clip scale are a pure function of the inputs.  Sums are kept in double (squares of floats
+// are exact there), so what remains of the fp32 contract's 1e-5 is the final rounding to float.
+__device__ inline void adam_at(const AdamSegs& s, int64_t i, float*& p, const float*& g) {
+  int lo = 0, hi = s.n - 1;  // the last tensor that starts at or before i (empty tensors share their offset)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (s.off[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  p = s.p[lo] + (i - s.off[lo]);
+  g = s.g[lo] + (i - s.off[lo]);
+}
+// g1: the gradient of the loss plus weight_decay_mult * sum p^2 / P;  g2: g1 clipped by value
+__device__ inline float adam_g1(float g, float p, float wdc) { return wdc != 0.0f ? g + wdc * p : g; }
+__device__ inline float adam_g2(float g1, float mv) { return mv > 0.0f ? fminf(fmaxf(g1, -mv), mv) : g1; }
+
+// x over the block's 256 threads; MAX: the largest, else the sum.  Every thread returns the same bits (the
+// butterfly adds the same pairs in every lane).  sh: 4 doubles that no other call of the kernel uses.
+template <bool MAX>
+__device__ inline double adam_block_reduce(double x, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, 64);
+    x = MAX ? fmax(x, y) : x + y;
+  }
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return MAX ? fmax(fmax(fmax(sh[0], sh[1]), sh[2]), sh[3]) : ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ __launch_bounds__(256) void k_adam_stats(int64_t n, const AdamSegs s, AdamOpts o,
+                                                    double* __restrict__ part) {
+  __shared__ double sh[4][4];
+  double s1 = 0.0, s2 = 0.0, sp = 0.0, mx = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float* pp;
+    const float* gp;
+    adam_at(s, i, pp, gp);
+    const float pi = *pp;
+    const float g1 = adam_g1(*gp, pi, o.wdc), g2 = adam_g2(g1, o.grad_max_val);
+    s1 += (double)g1 * (double)g1;
+    s2 += (double)g2 * (double)g2;
+    sp += (double)pi * (double)pi;
+    mx = fmax(mx, (double)fabsf(g1));
+  }
+  s1 = adam_block_reduce<false>(s1, sh[0]);
+  s2 = adam_block_reduce<false>(s2, sh[1]);
+  sp = adam_block_reduce<false>(sp, sh[2]);
+  mx = adam_block_reduce<true>(mx, sh[3]);
+  if (threadIdx.x == 0) {
+    part[0 * kAdamStatBlocks + blockIdx.x] = s1;
+    part[1 * kAdamStatBlocks + blockIdx.x] = s2;
+    part[2 * kAdamStatBlocks + blockIdx.x] = sp;
+    part[3 * kAdamStatBlocks + blockIdx.x] = mx;
+  }
+}
+
+// MOD: decay and clips applied (else the gradient as it is: k_adam's update, and only the record's block sums).
+// nb = the statistics pass's blocks (<= kAdamStatBlocks = blockDim).
+template <bool MOD>
+__global__ __launch_bounds__(256) void k_adam_opt(int64_t n, const AdamSegs s, float* __restrict__ m,
+                                                  float* __restrict__ v, float lr, float inv1, float inv2, AdamOpts o,
+                                                  const double* __restrict__ part, int nb, AdamStepStats* rec,
+                                                  int32_t iteration) {
+  __shared__ double sh[4][4];
+  const float b1 = 0.9f, b2 = 0.999f;
+  const int t = threadIdx.x;
+  float scale = 1.0f;
+  const bool writer = blockIdx.x == gridDim.x - 1;  // the record's block: the last one has the fewest elements
+  if (MOD || writer) {
+    const float n2 = (float)sqrt(adam_block_reduce<false>(t < nb ? part[1 * kAdamStatBlocks + t] : 0.0, sh[1]));
+    if (o.grad_max_norm > 0.0f) scale = fminf(1.0f, o.grad_max_norm / (1e-7f + n2));
+    if (writer) {
+      const double s1 = adam_block_reduce<false>(t < nb ? part[0 * kAdamStatBlocks + t] : 0.0, sh[0]);
+      const double sp = adam_block_reduce<false>(t < nb ? part[2 * kAdamStatBlocks + t] : 0.0, sh[2]);
+      const double mx = adam_block_reduce<true>(t < nb ? part[3 * kAdamStatBlocks + t] : 0.0, sh[3]);
+      if (t == 0) {
+        rec->weight_l2 = (float)(sp / (double)n);
+        rec->grad_norm = (float)sqrt(s1);
+        rec->grad_abs_max = (float)mx;
+        rec->grad_norm_clipped = scale * n2;
+        rec->clip_scale = scale;
+        rec->iteration = iteration;
+      }
+    }
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float* pp;
+    const float* gp;
+    adam_at(s, i, pp, gp);
+    const float pi = *pp;
+    float gi = *gp;
+    if (MOD) gi = adam_g2(adam_g1(gi, pi, o.wdc), o.grad_max_val) * scale;
+    const float mi = b1 * m[i] + (1.0f - b1) * gi;  // k_adam's sequence from here on
+    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float mh = mi * inv1, vh = vi * inv2;
+    *pp = pi - lr * mh * (1.0f / sqrtf(vh + 1e-8f));
+  }
+}
+
+static int adam_stat_blocks(int64_t total) {
+  const int64_t b = (total + 255) / 256;
+  return (int)(b < kAdamStatBlocks ? b : kAdamStatBlocks);
+}
+hipError_t launch_adam_stats(int64_t total, const AdamSegs& s, const AdamOpts& o, double* partials, hipStream_t st) {
+  if (total <= 0) return hipSuccess;
+  if (s.n < 1 || s.n > kAdamMaxSegs || s.off[0] != 0 || s.off[s.n] != total) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_adam_stats, dim3((unsigned)adam_stat_blocks(total)), dim3(256), 0, st, total, s, o, partials);
+  return hipGetLastError();
+}
+hipError_t launch_adam_opt(int64_t total, const AdamSegs& s, float* m, float* v, float lr, float inv1, float inv2,
+                           const AdamOpts& o, bool modify, const double* partials, AdamStepStats* record,
+                           int32_t iteration, hipStream_t st) {
+  if (total <= 0) return hipSuccess;
+  if (s.n < 1 || s.n > kAdamMaxSegs || s.off[0] != 0 || s.off[s.n] != total) return hipErrorInvalidValue;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  const int nb = adam_stat_blocks(total);
+  if (modify)
+    hipLaunchKernelGGL(k_adam_opt<true>, dim3((unsigned)blocks), dim3(256), 0, st, total, s, m, v, lr, inv1, inv2, o,
+                       partials, nb, record, iteration);
+  else
+    hipLaunchKernelGGL(k_adam_opt<false>, dim3((unsigned)blocks), dim3(256), 0, st, total, s, m, v, lr, inv1, inv2, o,
+                       partials, nb, record, iteration);
+  return hipGetLastError();
+}
+
 // Loopback all-reduce (dp.cpp, SURVEY §4's "loopback DP backend"): the K member buffers of one device
 // summed in member order (fp32, the same bits as adding them one after another) and written back to
 // every member.

@@ -281,6 +281,32 @@ constexpr int kLoopMax = 8;
 hipError_t launch_loopback_sum(int k, float* const* bufs, int64_t n, hipStream_t st);
 hipError_t launch_adam(int64_t n, float* p, const float* g, float* m, float* v, float lr, float inv1, float inv2,
                        hipStream_t st);
+// Adam's options (Config.GradMaxNorm / GradMaxVal / WeightDecayMult, TrainState.cs:58-59,70) and the step
+// statistics (StatsUtil.cs:13,16-18).  The parameter / gradient tensors as segments of one virtual arena:
+// tensor s holds elements [off[s], off[s + 1]); n = 1 for the flat arenas.  The moments are always flat.
+constexpr int kAdamStatBlocks = 256;  // most blocks of the statistics pass = most partials per sum
+constexpr int kAdamMaxSegs = 64;
+struct AdamSegs {
+  int n = 0;
+  int64_t off[kAdamMaxSegs + 1] = {};
+  float* p[kAdamMaxSegs] = {};
+  const float* g[kAdamMaxSegs] = {};
+};
+struct AdamOpts {
+  float grad_max_norm = 0.0f, grad_max_val = 0.0f;
+  float wdc = 0.0f;  // (2 weight_decay_mult) / P, 0 = no decay
+};
+struct AdamStepStats {  // = nof_step_stats (include/nof.h)
+  float weight_l2, grad_norm, grad_abs_max, grad_norm_clipped, clip_scale;
+  int32_t iteration;
+};
+// partials [4][kAdamStatBlocks] doubles: per-block sums of g1^2, g2^2, p^2 and the per-block max |g1|
+hipError_t launch_adam_stats(int64_t total, const AdamSegs& s, const AdamOpts& o, double* partials, hipStream_t st);
+// the update after launch_adam_stats(total, ...) on the same stream: one block writes *record; modify = apply
+// the decay and the clips (else k_adam's update on the gradient as it is)
+hipError_t launch_adam_opt(int64_t total, const AdamSegs& s, float* m, float* v, float lr, float inv1, float inv2,
+                           const AdamOpts& o, bool modify, const double* partials, AdamStepStats* record,
+                           int32_t iteration, hipStream_t st);
 // level 0's stratified t-values (k_sample_stratified's arguments), computable by the pack launch's extra blocks
 struct StratArgs {
   int n = 0, S = 0;  // rays, samples (n = 0: none)

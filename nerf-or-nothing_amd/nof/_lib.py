@@ -63,6 +63,11 @@ class nof_batch(C.Structure):
         "origins", "directions", "viewdirs", "radii", "nears", "fars", "loss_mults", "pixels", "record_index")]
 
 
+class nof_step_stats(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("weight_l2", "grad_norm", "grad_abs_max", "grad_norm_clipped",
+                                         "clip_scale")] + [("iteration", C.c_int32)]
+
+
 OUTPUT_GRAD_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_float, C.c_uint64)
 GRAD_BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 NOF_GRAD_ACCUMULATE, NOF_GRAD_PUBLISH, NOF_GRAD_BUCKETS = 1, 2, 2
@@ -145,6 +150,10 @@ SIGNATURES = {
     "nof_adam_step": [P, PP, PP, F],
     "nof_adam_iteration": [P, C.POINTER(I32)],
     "nof_adam_destroy": [P],
+    "nof_adam_set_options": [P, F, F, F, I32],
+    "nof_adam_get_options": [P, C.POINTER(F), C.POINTER(F), C.POINTER(F), C.POINTER(I32)],
+    "nof_adam_stats": [P, C.POINTER(nof_step_stats)],
+    "nof_adam_moments": [P, C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)],
     "nof_gradcalc_create": [I32, C.POINTER(nof_config), C.POINTER(P)],
     "nof_gradcalc_output_gradient": [P, U64, P, I32, U64, F, I32, C.POINTER(U64)],
     "nof_gradcalc_destroy": [P],

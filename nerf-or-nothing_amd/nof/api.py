@@ -356,20 +356,52 @@ class AcceleratedMipNeRF:
 
 
 class AcceleratedAdamOptimizer:
-    """AcceleratedAdamOptimizer.h:5-20; step = one fused launch over flat arenas."""
+    """AcceleratedAdamOptimizer.h:5-20; step = one fused launch over flat arenas.
 
-    def __init__(self, layer_sizes, config: L.nof_config | None = None):
+    grad_max_norm, grad_max_val, weight_decay_mult (Config.GradMaxNorm / GradMaxVal / WeightDecayMult,
+    TrainState.cs:58-59,70; 0 = off) and stats (gather the step statistics alone): include/nof.h
+    nof_adam_set_options.  With any of them set a step gathers the record that stats() returns."""
+
+    def __init__(self, layer_sizes, config: L.nof_config | None = None, grad_max_norm: float = 0.0,
+                 grad_max_val: float = 0.0, weight_decay_mult: float = 0.0, stats: bool = False):
         self.config = config if config is not None else L.default_config()
         arr = (C.c_int32 * len(layer_sizes))(*layer_sizes)
         self.n = len(layer_sizes)
         h = C.c_void_p()
         call("nof_adam_create", arr, len(layer_sizes), C.byref(self.config), C.byref(h))
         self._h = h
+        if grad_max_norm or grad_max_val or weight_decay_mult or stats:  # a NaN is truthy: refused below
+            self.set_options(grad_max_norm, grad_max_val, weight_decay_mult, stats)
+
+    def set_options(self, grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
+                    stats: bool = False):
+        """Negative or NaN values raise NofError (NOF_ERR_INVALID_ARG) and leave the options as they were."""
+        call("nof_adam_set_options", self._h, float(grad_max_norm), float(grad_max_val), float(weight_decay_mult),
+             int(bool(stats)))
+
+    def get_options(self) -> dict:
+        n, v, w, s = C.c_float(), C.c_float(), C.c_float(), C.c_int32()
+        call("nof_adam_get_options", self._h, C.byref(n), C.byref(v), C.byref(w), C.byref(s))
+        return {"grad_max_norm": n.value, "grad_max_val": v.value, "weight_decay_mult": w.value,
+                "stats": bool(s.value)}
+
+    def stats(self) -> dict:
+        """The last step's record (StatsUtil.cs:13,16-18 + clip_scale, iteration); synchronises the stream.
+        NofError when no step has gathered statistics."""
+        st = L.nof_step_stats()
+        call("nof_adam_stats", self._h, C.byref(st))
+        return {k: getattr(st, k) for k, _ in L.nof_step_stats._fields_}
 
     def step(self, params, grads, learning_rate: float):
         pa = (C.POINTER(C.c_float) * self.n)(*[C.cast(C.c_void_p(p), C.POINTER(C.c_float)) for p in params])
         ga = (C.POINTER(C.c_float) * self.n)(*[C.cast(C.c_void_p(g), C.POINTER(C.c_float)) for g in grads])
         call("nof_adam_step", self._h, pa, ga, float(learning_rate))
+
+    def moments(self):
+        """(m_ptr, v_ptr, count): the first and second moments, device pointers borrowed from the optimizer."""
+        m, v, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        call("nof_adam_moments", self._h, C.byref(m), C.byref(v), C.byref(n))
+        return m.value or 0, v.value or 0, n.value
 
     @property
     def iteration(self) -> int:

@@ -26,7 +26,8 @@ class Trainer:
     def __init__(self, dataset: api.RayDataset, batch_size: int = 1024, seed: int = 0x5EED0000, device: int = 0,
                  stream=None, print_every: int = 100, save_every: int = 0, ckpt_dir: str | None = None,
                  sync_check_every: int = 0, lr_init=5e-4, lr_final=5e-6, max_steps=1000000, lr_delay_steps=2500, lr_delay_mult=0.01,
-                 **config):
+                 grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
+                 stats: bool = False, **config):
         import torch.distributed as dist
 
         self.dist = dist if dist.is_available() and dist.is_initialized() else None
@@ -42,7 +43,13 @@ class Trainer:
                        lr_delay_mult=lr_delay_mult)
         self.cfg = default_config(device=device, max_rays=batch_size, seed=seed, stream=stream, **config)
         self.model = api.AcceleratedMipNeRF(self.cfg)
-        self.adam = api.AcceleratedAdamOptimizer(self.model.GetLayerSizes(), self.cfg)
+        # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70): hyper-parameters, not
+        # checkpoint state, so a resumed run passes them again
+        self.adam = api.AcceleratedAdamOptimizer(self.model.GetLayerSizes(), self.cfg, grad_max_norm=grad_max_norm,
+                                                 grad_max_val=grad_max_val, weight_decay_mult=weight_decay_mult,
+                                                 stats=stats)
+        self.with_stats = bool(stats or grad_max_norm or grad_max_val or weight_decay_mult)
+        self.last_stats = None  # the optimizer's record of the last print step (with_stats)
         self.params = self.model.mlp.allParams
         self.step_idx = 0  # completed steps (Program.cs counts from 1)
         self.device = device
@@ -91,8 +98,13 @@ class Trainer:
                 raise FloatingPointError(f"step {step}: non-finite values in the training step on some rank "
                                          f"(flags {bad:#x}; 1 = forward outputs, 2 = output gradients)")
             self.last_loss = self.fine_loss(b)
+            line = f"Step {step}/{self.lr['max_steps']}, Loss: {self.last_loss}"
+            if self.with_stats:  # StatsUtil.cs:13,16-18, of the all-reduced gradient (identical on every rank)
+                self.last_stats = st = self.adam.stats()
+                line += (f", grad_norm: {st['grad_norm']:.9g}, grad_abs_max: {st['grad_abs_max']:.9g}, "
+                         f"grad_norm_clipped: {st['grad_norm_clipped']:.9g}, weight_l2: {st['weight_l2']:.9g}")
             if self.rank == 0:
-                print(f"Step {step}/{self.lr['max_steps']}, Loss: {self.last_loss}", flush=True)
+                print(line, flush=True)
         if self.dist is not None and self.sync_check_every and step % self.sync_check_every == 0:
             self.check_sync()
         if self.save_every and self.ckpt_dir and step % self.save_every == 0 and self.rank == 0:
@@ -156,6 +168,11 @@ def main(argv=None):
     ap.add_argument("--cylinder", action="store_true")
     ap.add_argument("--density-bias", type=float, default=-1.0)
     ap.add_argument("--rgb-padding", type=float, default=0.001)
+    # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70; 0 = off) and the step statistics
+    ap.add_argument("--grad-max-norm", type=float, default=0.0, help="clip the gradient's global norm")
+    ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="weight_decay_mult of the loss term sum p^2 / P")
+    ap.add_argument("--stats", action="store_true", help="print the gradient statistics with the loss")
     a = ap.parse_args(argv)
     net = {k: getattr(a, k) for k in ("net_depth", "net_width", "net_depth_condition", "net_width_condition")
            if getattr(a, k) is not None}
@@ -167,6 +184,8 @@ def main(argv=None):
           api.RayDataset(records=synth.pack_records(synth.blender_rays(a.synthetic, seed=1)), device=a.device))
     tr = Trainer(ds, batch_size=a.batch, device=a.device, print_every=a.print_every, save_every=a.save_every,
                  ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
+                 grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
+                 stats=a.stats,
                  precision={"f32": 0, "split": 1, "f16x2": 2, "f16split": 3, "f16": 4}[a.precision], **net)
     if a.resume:
         tr.resume(a.resume)
