@@ -281,6 +281,41 @@ nof_status nof_generate_rays(const float* host_poses, int32_t num_views, int32_t
 nof_status nof_dataset_generate(const float* host_poses, int32_t num_views, int32_t width, int32_t height, float focal,
                                 float near_, float far_, int32_t ndc, const float* dev_images, int32_t device,
                                 nof_dataset** out);
+
+/* ---- multiscale, image-backed scenes ------------------------------------------------------------
+ * mip-NeRF trains on every image at several resolutions at once.  The reference declares the loader
+ * (DatasetType.Multicam, TrainState.cs:41,48) and never builds it (Multicam.LoadRenderings throws,
+ * Dataset.cs:203-207).  Here scale s of num_scales (1..4) is the image set halved s times: width >> s,
+ * height >> s, focal / 2^s (so a pixel's radius doubles per scale), the scene's near and far, and the
+ * loss multiplier 4^s.  nof_multiscale_layout fills the per-scale table (arrays of 4; entries past
+ * num_scales are 0) and the virtual record order: scale-major, then view-major, then row-major pixels,
+ * firsts[s] = num_views * sum_{j<s} w_j h_j, count = num_views * sum_s w_s h_s.  A batch's record_index maps
+ * back to (scale, view, y, x) through it.  Host only, no device.  NOF_ERR_INVALID_ARG: num_scales
+ * outside 1..4, width or height not divisible by 2^(num_scales-1), a last scale under 2 x 2,
+ * focal <= 0, count > 0xFFFFFFFF.
+ * disable_multiscale_loss != 0 is Config.DisableMultiscaleLoss (TrainState.cs:65): every scale's
+ * multiplier is 1. */
+nof_status nof_multiscale_layout(int32_t width, int32_t height, float focal, int32_t num_scales,
+                                 int32_t disable_multiscale_loss, int32_t num_views, int32_t* w /* [4] */,
+                                 int32_t* h /* [4] */, float* focals /* [4] */, float* lossmults /* [4] */,
+                                 int64_t* firsts /* [4] */, int64_t* count);
+/* The loader the reference leaves unbuilt (Dataset.cs:203-207), image-backed: the dataset keeps the
+ * poses and an image pyramid in HBM (12 bytes per ray in place of a 64-byte record) and
+ * nof_dataset_next generates each drawn record inside its gather launch, with the arithmetic of
+ * nof_generate_rays (bit-identical records).  dev_images: device [V][H][W][3] fp32, read only during
+ * the call (NULL: rgb = 0); pyramid level s is the 2 x 2 mean of level s-1,
+ * ((a + b) + (c + d)) * 0.25f over (2y,2x), (2y,2x+1), (2y+1,2x), (2y+1,2x+1) per channel in fp32.
+ * Arguments are refused as by nof_multiscale_layout (and null poses) before any device call.
+ * nof_dataset_count / _next / _is_streaming (0) / _destroy and nof_dp_train_step take the result. */
+nof_status nof_dataset_from_images(const float* host_poses, int32_t num_views, int32_t width, int32_t height,
+                                   float focal, float near_, float far_, int32_t ndc, const float* dev_images,
+                                   int32_t num_scales, int32_t disable_multiscale_loss, int32_t device,
+                                   nof_dataset** out);
+/* Every record of the dataset, in order, into dev_records (count x 16 floats, device), asynchronously
+ * on stream: what the Multicam loader of Dataset.cs:203-207 would have handed to BinDataset
+ * (BinDataset.cs:40-49), e.g. to write a multiscale record file.  Image-backed: generated; records
+ * resident in HBM: copied; streaming: NOF_ERR_UNSUPPORTED (the file is the record list). */
+nof_status nof_dataset_materialize(nof_dataset* ds, float* dev_records, void* stream);
 /* LLFFDataset.RecenterPoses (Dataset.cs:309-319) in place on host poses (V x 12). */
 nof_status nof_recenter_poses(float* host_poses, int32_t num_views);
 

@@ -305,6 +305,38 @@ nof_status nof_dataset_generate(const float* poses, int32_t V, int32_t w, int32_
     *out = d;
   });
 }
+nof_status nof_multiscale_layout(int32_t width, int32_t height, float focal, int32_t num_scales,
+                                 int32_t disable_multiscale_loss, int32_t num_views, int32_t* w, int32_t* h,
+                                 float* focals, float* lossmults, int64_t* firsts, int64_t* count) {
+  return guard([&] {
+    ARG(w && h && focals && lossmults && firsts && count);
+    const nof::MultiscaleLayout L =
+        multiscale_layout(width, height, focal, num_scales, disable_multiscale_loss, num_views);
+    for (int s = 0; s < nof::kMaxScales; ++s) {  // entries past num_scales are zero
+      w[s] = L.w[s]; h[s] = L.h[s]; focals[s] = L.focal[s]; lossmults[s] = L.lossmult[s]; firsts[s] = L.first[s];
+    }
+    *count = L.count;
+  });
+}
+nof_status nof_dataset_from_images(const float* poses, int32_t V, int32_t w, int32_t h, float focal, float near_,
+                                   float far_, int32_t ndc, const float* dev_images, int32_t num_scales,
+                                   int32_t disable_multiscale_loss, int32_t device, nof_dataset** out) {
+  return guard([&] {
+    ARG(out);
+    KEEP_DEVICE;
+    const ImageScene sc{poses, V, w, h, focal, near_, far_, ndc, dev_images, num_scales, disable_multiscale_loss};
+    auto* d = new nof_dataset{nullptr};
+    try { d->impl = new RayDataset(sc, device); } catch (...) { delete d; throw; }
+    *out = d;
+  });
+}
+nof_status nof_dataset_materialize(nof_dataset* ds, float* dev_records, void* stream) {
+  return guard([&] {
+    ARG(ds && dev_records);
+    DEV(ds);
+    ds->impl->materialize(dev_records, (hipStream_t)stream);
+  });
+}
 nof_status nof_recenter_poses(float* poses, int32_t V) {
   return guard([&] { recenter_poses(poses, V); });
 }

@@ -90,6 +90,58 @@ RayDataset::RayDataset(const float* host_poses, int V, int w, int h, float focal
   NOF_HIP(hipStreamSynchronize(nullptr));
 }
 
+nof::MultiscaleLayout multiscale_layout(int width, int height, float focal, int num_scales,
+                                        int disable_multiscale_loss, int num_views) {
+  NOF_REQUIRE(num_scales >= 1 && num_scales <= nof::kMaxScales, "num_scales must be 1..4");
+  NOF_REQUIRE(num_views > 0 && width > 0 && height > 0, "bad image set");
+  NOF_REQUIRE(focal > 0.0f, "focal length must be positive");
+  const int div = 1 << (num_scales - 1);
+  NOF_REQUIRE(width % div == 0 && height % div == 0, "width and height must be divisible by 2^(num_scales - 1)");
+  NOF_REQUIRE(width / div >= 2 && height / div >= 2, "the smallest scale must be at least 2 x 2");
+  nof::MultiscaleLayout L{};
+  L.num_scales = num_scales;
+  L.num_views = num_views;
+  int64_t first = 0;
+  for (int s = 0; s < num_scales; ++s) {  // halving and 4^s are exact in fp32
+    L.w[s] = width >> s;
+    L.h[s] = height >> s;
+    L.focal[s] = focal / (float)(1 << s);
+    L.lossmult[s] = disable_multiscale_loss ? 1.0f : (float)(1 << (2 * s));
+    L.first[s] = first;
+    first += (int64_t)num_views * L.w[s] * L.h[s];
+  }
+  L.count = first;
+  NOF_REQUIRE(L.count <= 0xFFFFFFFFll, "too many rays");
+  return L;
+}
+
+RayDataset::RayDataset(const ImageScene& sc, int device) : device_(device) {
+  NOF_REQUIRE(sc.host_poses != nullptr, "null poses");
+  layout_ = multiscale_layout(sc.width, sc.height, sc.focal, sc.num_scales, sc.disable_multiscale_loss, sc.num_views);
+  count_ = layout_.count;
+  near_ = sc.near; far_ = sc.far; ndc_ = sc.ndc;
+  NOF_HIP(hipSetDevice(device));
+  poses_.alloc((size_t)sc.num_views * 12);
+  NOF_HIP(hipMemcpy(poses_.p, sc.host_poses, (size_t)sc.num_views * 12 * sizeof(float), hipMemcpyHostToDevice));
+  if (sc.dev_images) {  // all levels in one allocation, in record order
+    pyr_.alloc((size_t)count_ * 3);
+    const size_t level0 = (size_t)sc.num_views * sc.width * sc.height * 3 * sizeof(float);
+    NOF_HIP(hipMemcpyAsync(pyr_.p, sc.dev_images, level0, hipMemcpyDeviceToDevice, nullptr));
+    for (int s = 1; s < layout_.num_scales; ++s) NOF_HIP(nof::launch_pyramid_level(pyr_.p, layout_, s, nullptr));
+    NOF_HIP(hipStreamSynchronize(nullptr));  // the caller's images are only read during this call
+  }
+}
+
+void RayDataset::materialize(float* dev_records, hipStream_t st) {
+  NOF_REQUIRE(dev_records != nullptr, "null record buffer");
+  if (streaming()) throw Error(NOF_ERR_UNSUPPORTED, "a streaming dataset's records are in its file");
+  NOF_HIP(hipSetDevice(device_));
+  if (image_backed())
+    NOF_HIP(nof::launch_materialize(poses_.p, pyr_.p, layout_, near_, far_, ndc_, dev_records, st));
+  else
+    NOF_HIP(hipMemcpyAsync(dev_records, rec_.p, (size_t)count_ * 64, hipMemcpyDeviceToDevice, st));
+}
+
 void generate_rays(const float* host_poses, int V, int w, int h, float focal, float near, float far, int ndc,
                    const float* dev_images, float* dev_records, hipStream_t st) {
   NOF_REQUIRE(host_poses && dev_records && V > 0 && w > 1 && h > 1 && focal > 0.0f, "bad ray-generation arguments");
@@ -186,8 +238,13 @@ void RayDataset::next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hi
     cur_key_ = want;
     staged = 1;
   }
-  NOF_HIP(nof::launch_gather_batch(rec_.p, count_, n, seed, step, ray_base, o_.p, d_.p, vd_.p, r_.p, nr_.p, fr_.p,
-                                   lm_.p, pix_.p, idx_.p, host_msum ? msum_.p : nullptr, st, staged));
+  if (image_backed())  // no records: the gather generates the drawn ones
+    NOF_HIP(nof::launch_gather_rays(poses_.p, pyr_.p, layout_, near_, far_, ndc_, n, seed, step, ray_base, o_.p, d_.p,
+                                    vd_.p, r_.p, nr_.p, fr_.p, lm_.p, pix_.p, idx_.p, host_msum ? msum_.p : nullptr,
+                                    st));
+  else
+    NOF_HIP(nof::launch_gather_batch(rec_.p, count_, n, seed, step, ray_base, o_.p, d_.p, vd_.p, r_.p, nr_.p, fr_.p,
+                                     lm_.p, pix_.p, idx_.p, host_msum ? msum_.p : nullptr, st, staged));
   if (streaming()) {
     NOF_HIP(hipEventRecord(gathered_, st));
     // prefetch the likely next request (the next step of the same shard) into the other buffer while

@@ -1,6 +1,7 @@
 // Data path and training-state persistence around the hot path:
 //   * RayDataset — BinDataset (BinDataset.cs:10-53) made device-resident: the 64-byte records live
 //     in HBM and a batch is one gather launch (dataset.hip) instead of 1024 file seeks per step;
+//     or image-backed: poses and an image pyramid in HBM, the rays generated in the batch gather;
 //   * checkpoints — Config.SaveEvery (TrainState.cs:59) is declared but never implemented by the
 //     reference; here a step's full state (parameters, Adam moments and step, Philox state) is
 //     written and restored bit-exactly.
@@ -10,6 +11,20 @@
 #include "accelerated.h"
 
 namespace AcceleratedNeRFUtils {
+
+// A scene for the image-backed dataset: poses (host, V x [R row-major | t]), full-resolution device
+// images [V][H][W][3] (or null: rgb = 0), trained at num_scales resolutions (multiscale_layout).
+struct ImageScene {
+  const float* host_poses;
+  int num_views, width, height;
+  float focal, near, far;
+  int ndc;
+  const float* dev_images;
+  int num_scales, disable_multiscale_loss;
+};
+// The multiscale record layout (launch.h), or NOF_ERR_INVALID_ARG; needs no device.
+nof::MultiscaleLayout multiscale_layout(int width, int height, float focal, int num_scales,
+                                        int disable_multiscale_loss, int num_views);
 
 class RayDataset {
  public:
@@ -24,9 +39,16 @@ class RayDataset {
   // generate the records on the device from poses (V x 12 floats, host) and optional device images
   RayDataset(const float* host_poses, int V, int w, int h, float focal, float near, float far, int ndc,
              const float* dev_images, int device);
+  // Image-backed: the pose table and the image pyramid (level 0 copied from scene.dev_images, which
+  // is only read during the call) stay in HBM; no record is stored, next() generates the drawn ones.
+  RayDataset(const ImageScene& scene, int device);
   int64_t count() const { return count_; }
   int device() const { return device_; }
   bool streaming() const { return fd_ >= 0; }
+  bool image_backed() const { return poses_.p != nullptr; }
+  // Every record in order into dev_records (count x 16 floats): generated for an image-backed
+  // dataset, copied for a resident one; a streaming dataset refuses (NOF_ERR_UNSUPPORTED).
+  void materialize(float* dev_records, hipStream_t st);
   // Gather n records for (seed, step, first global ray id); device SoA views owned by the dataset
   // (valid until the next call).  host_msum != null: also the loss-multiplier sum (synchronises st).
   void next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hipStream_t st, nof_batch* out, float* host_msum);
@@ -37,7 +59,14 @@ class RayDataset {
   void fetch(int b, int n, uint64_t seed, uint32_t step, uint32_t ray_base);
   int device_;
   int64_t count_ = 0;
+  // resident: every record; streaming: the staging slot of one batch; image-backed: unused
   DevBuf<float> rec_;
+  // image-backed state: the layout, the scene's constants, the pose table (V x 12) and the pyramid
+  // (count x 3 floats in record order; unallocated for a scene without images)
+  nof::MultiscaleLayout layout_{};
+  float near_ = 0.0f, far_ = 0.0f;
+  int ndc_ = 0;
+  DevBuf<float> poses_, pyr_;
   // streaming state: the file, two pinned record buffers (n x 64 B), the device staging slots, the
   // event after each buffer's last copy, and the prefetch (its key and its host thread)
   int fd_ = -1;

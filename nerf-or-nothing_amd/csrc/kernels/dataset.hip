@@ -7,8 +7,11 @@
 // (D2: Philox replaces the unseeded System.Random), so a sharded batch draws the same records as the
 // whole batch.  One thread per (ray, 16-B quarter of its 64-B record): coalesced 64-B record reads,
 // SoA writes.  The loss-multiplier sum is a fixed-order block reduction (deterministic).
-#include "common.h"
-#include "launch.h"
+//
+// An image-backed scene (include/nof.h nof_dataset_from_images) holds no records: its gather,
+// k_gather_rays, draws the same indices and generates each drawn record from its pose and its pixel
+// of the image pyramid with raygen.h's per-ray function, one thread per ray.
+#include "raygen.h"
 
 namespace nof {
 
@@ -51,6 +54,35 @@ __global__ __launch_bounds__(256) void k_gather_batch(const float4* __restrict__
   }
 }
 
+// Rays per block of k_gather_rays.  A batch is small (1024 rays) and a ray is a dependent chain of pose
+// loads, divides and square roots, so one wave per block spreads the batch over the most CUs
+// (DESIGN.md has the measurement against 256).
+#ifndef NOF_GATHER_RAYS_BLOCK
+#define NOF_GATHER_RAYS_BLOCK 64
+#endif
+constexpr int kGatherRaysBlock = NOF_GATHER_RAYS_BLOCK;
+
+__global__ __launch_bounds__(kGatherRaysBlock) void k_gather_rays(
+    const float* __restrict__ poses, const float* __restrict__ pyr, MultiscaleLayout L, float near_, float far_,
+    int ndc, int n, uint64_t seed, uint32_t step, uint32_t ray_base, float* __restrict__ o, float* __restrict__ d,
+    float* __restrict__ vd, float* __restrict__ radius, float* __restrict__ near, float* __restrict__ far,
+    float* __restrict__ lm, float* __restrict__ pix, int* __restrict__ idx_out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const uint32_t idx = batch_record(seed, step, ray_base + (uint32_t)r, L.count);
+  const RecordPos p = record_pos(L, idx);
+  NOF_DCHECK((int64_t)idx < L.count && p.v < L.num_views && p.x < p.w && p.y < p.h, kChkGather);
+  const Ray ray = ray_at(poses + 12 * p.v, p.x, p.y, p.w, p.h, p.focal, ndc);
+  const float* px = pyr ? pyr + (int64_t)idx * 3 : nullptr;  // the pyramid is stored in record order
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    o[3 * r + k] = ray.o[k]; d[3 * r + k] = ray.d[k]; vd[3 * r + k] = ray.vd[k];
+    pix[3 * r + k] = px ? px[k] : 0.0f;
+  }
+  radius[r] = ray.radius; near[r] = near_; far[r] = far_; lm[r] = p.lossmult;
+  if (idx_out) idx_out[r] = (int)idx;
+}
+
 __global__ __launch_bounds__(1024) void k_sum(const float* __restrict__ x, int n, float* __restrict__ out) {
   __shared__ float red[1024];
   float s = 0.0f;
@@ -79,6 +111,19 @@ hipError_t launch_gather_batch(const float* records, int64_t count, int n, uint6
   hipLaunchKernelGGL(k_gather_batch, dim3((4 * n + 255) / 256), dim3(256), 0, st,
                      reinterpret_cast<const float4*>(records), count, n, seed, step, ray_base, o, d, vd, radius,
                      near, far, lm, pix, idx_out, staged);
+  if (lm_sum) hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, st, lm, n, lm_sum);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_rays(const float* poses, const float* pyr, const MultiscaleLayout& L, float near, float far,
+                              int ndc, int n, uint64_t seed, uint32_t step, uint32_t ray_base, float* o, float* d,
+                              float* vd, float* radius, float* nears, float* fars, float* lm, float* pix, int* idx_out,
+                              float* lm_sum, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (L.count <= 0 || L.count > 0xFFFFFFFFll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_gather_rays, dim3((n + kGatherRaysBlock - 1) / kGatherRaysBlock), dim3(kGatherRaysBlock), 0,
+                     st, poses, pyr, L, near, far, ndc, n, seed, step, ray_base, o, d, vd, radius, nears, fars, lm,
+                     pix, idx_out);
   if (lm_sum) hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, st, lm, n, lm_sum);
   return hipGetLastError();
 }

@@ -272,6 +272,32 @@ uint32_t batch_record_host(uint64_t seed, uint32_t step, uint32_t gray, int64_t 
 hipError_t launch_generate_rays(const float* poses, int V, int w, int h, float focal, float near, float far, int ndc,
                                 const float* images, float* records, hipStream_t st);
 
+// ---- multiscale scenes (include/nof.h nof_multiscale_layout): images at num_scales resolutions ----
+// Scale s halves width, height and focal length s times and weighs its rays by lossmult[s].  The
+// virtual records are scale-major, then view-major, then row-major pixels: first[s] is scale s's first
+// record, and, the image pyramid being stored in the same order, also its first pixel.  Passed to the
+// kernels by value.
+constexpr int kMaxScales = 4;
+struct MultiscaleLayout {
+  int num_scales, num_views;
+  int w[kMaxScales], h[kMaxScales];
+  float focal[kMaxScales], lossmult[kMaxScales];
+  int64_t first[kMaxScales];
+  int64_t count;
+};
+// raygen.hip: pyramid level s from level s - 1 of the same allocation (pyr: count x 3 floats, level 0
+// filled by the caller): p = ((a + b) + (c + d)) * 0.25f over each 2 x 2 block, per channel
+hipError_t launch_pyramid_level(float* pyr, const MultiscaleLayout& L, int s, hipStream_t st);
+// raygen.hip: every virtual record in order (count x 16 floats); pyr == nullptr: rgb = 0
+hipError_t launch_materialize(const float* poses, const float* pyr, const MultiscaleLayout& L, float near, float far,
+                              int ndc, float* records, hipStream_t st);
+// dataset.hip: launch_gather_batch for an image-backed scene: each drawn record is generated in the
+// gather from its pose and pyramid pixel instead of being read
+hipError_t launch_gather_rays(const float* poses, const float* pyr, const MultiscaleLayout& L, float near, float far,
+                              int ndc, int n, uint64_t seed, uint32_t step, uint32_t ray_base, float* o, float* d,
+                              float* vd, float* radius, float* nears, float* fars, float* lm, float* pix, int* idx_out,
+                              float* lm_sum, hipStream_t st);
+
 // ---- metrics.hip: PSNR / SSIM of device images [H][W][3] (synchronises st) ----
 hipError_t image_metrics(const float* a, const float* b, int W, int H, float max_val, float* psnr, float* ssim,
                          hipStream_t st);

@@ -4,45 +4,23 @@
 // the GPU from poses (+ images) and gathered by dataset.hip.
 //
 // One thread per pixel; neighbours' directions / NDC origins are recomputed, not exchanged.  Every
-// expression keeps the C# evaluation order in fp32 and the file is compiled without FMA contraction,
-// so records are bit-identical to the oracle (oracle/raygen.py).
-#include "common.h"
-#include "launch.h"
-
-#pragma clang fp contract(off)
+// expression keeps the C# evaluation order in fp32 and the file is compiled without FMA contraction
+// (raygen.h), so records are bit-identical to the oracle (oracle/raygen.py).
+//
+// Multiscale scenes (the DatasetType.Multicam loader the reference declares, TrainState.cs:41, and
+// never builds, Dataset.cs:203-207): the image pyramid, and the materialiser that writes every
+// virtual record of such a scene through the same per-ray function.
+#include "raygen.h"
 
 namespace nof {
 
-// cameraDirs[y, x] then rotation * dir (Dataset.cs:118-141; Matrix3x3 * Vector3, MipHelpers.cs:36-40).
-// P = pose: rotation row-major (Matrix3x3 _m11.._m33) then translation.
-__device__ inline void pixel_dir(const float* __restrict__ P, int x, int y, int w, int h, float focal, float d[3]) {
-  const float cx = ((float)x - (float)w * 0.5f + 0.5f) / focal;
-  const float cy = -((float)y - (float)h * 0.5f + 0.5f) / focal;
-  const float cz = -1.0f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) d[i] = P[3 * i] * cx + P[3 * i + 1] * cy + P[3 * i + 2] * cz;
-}
-
-__device__ inline float len3(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
-
-// ConvertToNdc (Dataset.cs:295-308), near = 1
-__device__ inline void to_ndc(const float o_in[3], const float d[3], float focal, float w, float h, float on[3],
-                              float dn[3]) {
-  const float nearp = 1.0f;
-  const float t = -(nearp + o_in[2]) / d[2];
-  const float ox = o_in[0] + t * d[0], oy = o_in[1] + t * d[1], oz = o_in[2] + t * d[2];
-  on[0] = -(2.0f * focal / w) * (ox / oz);
-  on[1] = -(2.0f * focal / h) * (oy / oz);
-  on[2] = 1.0f + 2.0f * nearp / oz;
-  dn[0] = -(2.0f * focal / w) * (d[0] / d[2] - ox / oz);
-  dn[1] = -(2.0f * focal / h) * (d[1] / d[2] - oy / oz);
-  dn[2] = -2.0f * nearp / oz;
-}
-
-__device__ inline void ndc_origin(const float* __restrict__ P, int x, int y, int w, int h, float focal, float on[3]) {
-  float d[3], dn[3];
-  pixel_dir(P, x, y, w, h, focal, d);
-  to_ndc(P + 9, d, focal, (float)w, (float)h, on, dn);
+__device__ inline void store_record(float* __restrict__ rec, const Ray& r, float near, float far, float lossmult,
+                                    const float* __restrict__ px) {
+  float4* q = reinterpret_cast<float4*>(rec);
+  q[0] = make_float4(r.o[0], r.o[1], r.o[2], r.d[0]);
+  q[1] = make_float4(r.d[1], r.d[2], r.vd[0], r.vd[1]);
+  q[2] = make_float4(r.vd[2], r.radius, near, far);
+  q[3] = make_float4(lossmult, px ? px[0] : 0.0f, px ? px[1] : 0.0f, px ? px[2] : 0.0f);
 }
 
 __global__ __launch_bounds__(256) void k_generate_rays(const float* __restrict__ poses, int V, int w, int h,
@@ -53,38 +31,8 @@ __global__ __launch_bounds__(256) void k_generate_rays(const float* __restrict__
   if (g >= per * V) return;
   const int v = (int)(g / per), p = (int)(g - (int64_t)v * per);
   const int y = p / w, x = p - y * w;
-  const float* P = poses + 12 * v;
-  float d[3];
-  pixel_dir(P, x, y, w, h, focal, d);
-  const float dl = len3(d[0], d[1], d[2]);
-  const float vd[3] = {d[0] / dl, d[1] / dl, d[2] / dl};  // Vector3.Normalize (pre-NDC direction)
-  float o[3] = {P[9], P[10], P[11]}, dd[3] = {d[0], d[1], d[2]};
-  float radius;
-  if (!ndc) {  // Dataset.cs:144-152: neighbour to the right, itself in the last column (radius 0)
-    const int nx = x < w - 1 ? x + 1 : x;
-    float dn[3];
-    pixel_dir(P, nx, y, w, h, focal, dn);
-    radius = len3(d[0] - dn[0], d[1] - dn[1], d[2] - dn[2]) * 2.0f / sqrtf(12.0f);
-  } else {  // Dataset.cs:272-289: NDC warp, radius from the NDC origins of the x / y neighbours
-    float on[3], dnd[3];
-    to_ndc(o, d, focal, (float)w, (float)h, on, dnd);
-    float a[3], b[3];
-    if (x < w - 1) { ndc_origin(P, x + 1, y, w, h, focal, b); a[0] = on[0]; a[1] = on[1]; a[2] = on[2]; }
-    else { ndc_origin(P, x - 1, y, w, h, focal, a); b[0] = on[0]; b[1] = on[1]; b[2] = on[2]; }
-    const float dx = len3(a[0] - b[0], a[1] - b[1], a[2] - b[2]);
-    if (y < h - 1) { ndc_origin(P, x, y + 1, w, h, focal, b); a[0] = on[0]; a[1] = on[1]; a[2] = on[2]; }
-    else { ndc_origin(P, x, y - 1, w, h, focal, a); b[0] = on[0]; b[1] = on[1]; b[2] = on[2]; }
-    const float dy = len3(a[0] - b[0], a[1] - b[1], a[2] - b[2]);
-    radius = sqrtf(dx * dx + dy * dy) / sqrtf(12.0f);
-    o[0] = on[0]; o[1] = on[1]; o[2] = on[2];
-    dd[0] = dnd[0]; dd[1] = dnd[1]; dd[2] = dnd[2];
-  }
-  float4* r = reinterpret_cast<float4*>(rec + g * 16);
-  const float* px = images ? images + g * 3 : nullptr;
-  r[0] = make_float4(o[0], o[1], o[2], dd[0]);
-  r[1] = make_float4(dd[1], dd[2], vd[0], vd[1]);
-  r[2] = make_float4(vd[2], radius, near, far);
-  r[3] = make_float4(1.0f, px ? px[0] : 0.0f, px ? px[1] : 0.0f, px ? px[2] : 0.0f);  // LossMult = 1
+  const Ray r = ray_at(poses + 12 * v, x, y, w, h, focal, ndc);
+  store_record(rec + g * 16, r, near, far, 1.0f, images ? images + g * 3 : nullptr);  // LossMult = 1
 }
 
 hipError_t launch_generate_rays(const float* poses, int V, int w, int h, float focal, float near, float far, int ndc,
@@ -93,6 +41,47 @@ hipError_t launch_generate_rays(const float* poses, int V, int w, int h, float f
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_generate_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, poses, V, w, h, focal,
                      near, far, ndc, images, records);
+  return hipGetLastError();
+}
+
+// One thread per output pixel of level s: V views of w x h from V views of 2w x 2h, all three channels.
+__global__ __launch_bounds__(256) void k_pyramid_level(const float* __restrict__ src, float* __restrict__ dst,
+                                                       int64_t n, int w, int h) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const int64_t per = (int64_t)w * h;
+  const int64_t v = g / per;
+  const int p = (int)(g - v * per);
+  const int y = p / w, x = p - y * w;
+  const float* a = src + ((v * 2 * h + 2 * y) * (2 * (int64_t)w) + 2 * x) * 3;  // (2y, 2x); b follows it
+  const float* c = a + 2 * (int64_t)w * 3;                                    // (2y + 1, 2x); d follows it
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dst[g * 3 + k] = ((a[k] + a[3 + k]) + (c[k] + c[3 + k])) * 0.25f;
+}
+
+hipError_t launch_pyramid_level(float* pyr, const MultiscaleLayout& L, int s, hipStream_t st) {
+  if (s < 1 || s >= L.num_scales) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)L.num_views * L.w[s] * L.h[s];
+  hipLaunchKernelGGL(k_pyramid_level, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pyr + L.first[s - 1] * 3,
+                     pyr + L.first[s] * 3, n, L.w[s], L.h[s]);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void k_materialize(const float* __restrict__ poses, const float* __restrict__ pyr,
+                                                     MultiscaleLayout L, float near, float far, int ndc,
+                                                     float* __restrict__ rec) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= L.count) return;
+  const RecordPos p = record_pos(L, (uint32_t)g);
+  const Ray r = ray_at(poses + 12 * p.v, p.x, p.y, p.w, p.h, p.focal, ndc);
+  store_record(rec + g * 16, r, near, far, p.lossmult, pyr ? pyr + g * 3 : nullptr);
+}
+
+hipError_t launch_materialize(const float* poses, const float* pyr, const MultiscaleLayout& L, float near, float far,
+                              int ndc, float* records, hipStream_t st) {
+  if (L.count <= 0 || L.count > 0xFFFFFFFFll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_materialize, dim3((unsigned)((L.count + 255) / 256)), dim3(256), 0, st, poses, pyr, L, near,
+                     far, ndc, records);
   return hipGetLastError();
 }
 

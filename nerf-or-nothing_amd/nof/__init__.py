@@ -24,5 +24,6 @@ from .api import (  # noqa: F401
     grad_bucket_spans,
     image_metrics,
     learning_rate_decay,
+    multiscale_layout,
     to_numpy,
 )

@@ -114,6 +114,10 @@ SIGNATURES = {
     "nof_dataset_destroy": [P],
     "nof_generate_rays": [P, I32, I32, I32, F, F, F, I32, P, P, P],
     "nof_dataset_generate": [P, I32, I32, I32, F, F, F, I32, P, I32, C.POINTER(P)],
+    "nof_multiscale_layout": [I32, I32, F, I32, I32, I32, C.POINTER(I32), C.POINTER(I32), C.POINTER(F),
+                              C.POINTER(F), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "nof_dataset_from_images": [P, I32, I32, I32, F, F, F, I32, P, I32, I32, I32, C.POINTER(P)],
+    "nof_dataset_materialize": [P, P, P],
     "nof_recenter_poses": [P, I32],
     "nof_dp_unique_id": [P],
     "nof_dp_init_rank": [P, I32, I32, I32, C.POINTER(P)],

@@ -466,13 +466,23 @@ class RayDataset:
               "near": ("nears", 1), "far": ("fars", 1), "lossmult": ("loss_mults", 1), "pix": ("pixels", 3)}
 
     def __init__(self, path=None, records=None, device: int = 0, generate: dict | None = None,
-                 max_resident: int | None = None):
+                 max_resident: int | None = None, scene: dict | None = None):
         """path: record file (max_resident: HBM-resident iff at most that many records, else streamed
         from the file per batch); records: host [N, 16] array; generate: dict(poses [V, 12], width,
         height, focal, near, far, ndc=False, images=device tensor [V, H, W, 3] or None) -> rays made on
-        the GPU."""
+        the GPU; scene: the same dict plus num_scales=1 and multiscale_loss=True -> image-backed: poses
+        and an image pyramid stay in HBM and each batch's rays are made in its gather, at num_scales
+        resolutions (multiscale_layout)."""
         h = C.c_void_p()
-        if generate is not None:
+        if scene is not None:
+            g = dict(scene)
+            poses = np.ascontiguousarray(g["poses"], dtype=np.float32).reshape(-1, 12)
+            img = g.get("images")
+            call("nof_dataset_from_images", poses.ctypes.data, poses.shape[0], int(g["width"]), int(g["height"]),
+                 float(g["focal"]), float(g["near"]), float(g["far"]), int(bool(g.get("ndc", False))),
+                 _ptr(img) if img is not None else None, int(g.get("num_scales", 1)),
+                 int(not g.get("multiscale_loss", True)), device, C.byref(h))
+        elif generate is not None:
             g = dict(generate)
             poses = np.ascontiguousarray(g["poses"], dtype=np.float32).reshape(-1, 12)
             img = g.get("images")
@@ -487,6 +497,7 @@ class RayDataset:
             rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 16)
             call("nof_dataset_from_host", rec.ctypes.data, rec.shape[0], device, C.byref(h))
         self._h = h
+        self._device = device
 
     def __len__(self):
         n = C.c_int64()
@@ -508,6 +519,16 @@ class RayDataset:
         out = {k: (getattr(b, f), (n, w) if w > 1 else (n,)) for k, (f, w) in self.FIELDS.items()}
         out["record_index"] = (b.record_index, (n,))
         return out, (msum.value if with_sum else None)
+
+    def materialize(self, stream=None):
+        """Every record in order -> device tensor [count, 16] (torch): generated for an image-backed
+        dataset, copied for a resident one; a streaming dataset raises NofError(NOF_ERR_UNSUPPORTED)."""
+        import torch
+
+        out = torch.empty((len(self), 16), dtype=torch.float32, device=torch.device("cuda", self._device))
+        call("nof_dataset_materialize", self._h, out.data_ptr(), stream)
+        torch.cuda.synchronize(self._device)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -532,6 +553,19 @@ def generate_rays(poses, width, height, focal, near, far, ndc=False, images=None
     call("nof_generate_rays", poses.ctypes.data, poses.shape[0], int(width), int(height), float(focal), float(near),
          float(far), int(bool(ndc)), _ptr(images) if images is not None else None, out.data_ptr(), stream)
     return out
+
+
+def multiscale_layout(width, height, focal, num_scales=1, multiscale_loss=True, num_views=1) -> dict:
+    """The record layout of a multiscale scene (host only): per scale the width, height, focal length,
+    loss multiplier and first record, and the record count.  scale, view, y, x of record i:
+    s = the last scale with first[s] <= i, then divmod of i - first[s] by width[s] * height[s] and width[s]."""
+    S = int(num_scales)
+    w, h, first = (C.c_int32 * 4)(), (C.c_int32 * 4)(), (C.c_int64 * 4)()
+    f, lm, count = (C.c_float * 4)(), (C.c_float * 4)(), C.c_int64()
+    call("nof_multiscale_layout", int(width), int(height), float(focal), S, int(not multiscale_loss), int(num_views),
+         w, h, f, lm, first, C.byref(count))
+    return dict(width=list(w[:S]), height=list(h[:S]), focal=list(f[:S]), lossmult=list(lm[:S]),
+                first=list(first[:S]), count=count.value)
 
 
 def recenter_poses(poses) -> np.ndarray:

@@ -4,6 +4,7 @@ never implements.
 
     python -m nof.train --records train_data.bin --steps 1000 [--ckpt-dir ck --save-every 500 --resume]
     python -m nof.train --synthetic 100000 --steps 200          (Lego-shaped synthetic records)
+    python -m nof.train --scene scene.npz --num-scales 4        (poses + images, rays made per batch)
 
 One step = dataset batch (device gather) -> AcceleratedMipNeRF.get_gradient_device (fused loss
 gradient) -> [all-reduce of the gradient arena when torch.distributed is initialised] ->
@@ -139,6 +140,21 @@ class Trainer:
         return self
 
 
+def scene_dataset(path, num_scales=1, multiscale_loss=True, device=0) -> api.RayDataset:
+    """The image-backed dataset of a scene file (.npz: poses [V,12], images [V,H,W,3], focal, near, far,
+    optional ndc)."""
+    import torch
+
+    z = np.load(path)
+    images = torch.from_numpy(np.ascontiguousarray(z["images"], dtype=np.float32)).to(torch.device("cuda", device))
+    V, H, W, _ = images.shape
+    assert z["poses"].size == V * 12, "poses must be [V, 12] for images [V, H, W, 3]"
+    return api.RayDataset(device=device, scene=dict(
+        poses=z["poses"], width=W, height=H, focal=float(z["focal"]), near=float(z["near"]), far=float(z["far"]),
+        ndc=bool(z["ndc"]) if "ndc" in z else False, images=images, num_scales=num_scales,
+        multiscale_loss=multiscale_loss))
+
+
 def main(argv=None):
     from . import synth
 
@@ -146,6 +162,11 @@ def main(argv=None):
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--records", help="BinDataset file of 64-byte records")
     src.add_argument("--synthetic", type=int, help="number of synthetic Lego-shaped records")
+    src.add_argument("--scene", help=".npz of poses [V,12], images [V,H,W,3], focal, near, far and optional ndc: "
+                                     "an image-backed dataset (rays generated in each batch's gather)")
+    ap.add_argument("--num-scales", type=int, default=1, help="--scene: train on the images at 1..4 resolutions")
+    ap.add_argument("--disable-multiscale-loss", action="store_true",
+                    help="--scene: loss multiplier 1 at every scale instead of 4^scale")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--device", type=int, default=0)
@@ -180,8 +201,12 @@ def main(argv=None):
         net["num_samples"] = tuple(a.samples)
     net.update(lindisp=int(a.lindisp), ray_shape=int(a.cylinder), density_bias=a.density_bias,
                rgb_padding=a.rgb_padding)
-    ds = (api.RayDataset(a.records, device=a.device) if a.records else
-          api.RayDataset(records=synth.pack_records(synth.blender_rays(a.synthetic, seed=1)), device=a.device))
+    if a.scene:
+        ds = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device)
+    elif a.records:
+        ds = api.RayDataset(a.records, device=a.device)
+    else:
+        ds = api.RayDataset(records=synth.pack_records(synth.blender_rays(a.synthetic, seed=1)), device=a.device)
     tr = Trainer(ds, batch_size=a.batch, device=a.device, print_every=a.print_every, save_every=a.save_every,
                  ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
                  grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
