@@ -390,6 +390,57 @@ nof_status nof_dp_train_step(int32_t n, nof_dp* const* dps, nof_mipnerf* const* 
 nof_status nof_image_metrics(const float* dev_img0, const float* dev_img1, int32_t width, int32_t height,
                              float max_val, float* psnr, float* ssim, void* stream);
 
+/* ---- the test split: whole views rendered and scored on the device ------------------------------
+ * The reference declares the test side and leaves it empty: Split.Test (Dataset.cs:13-17) whose
+ * TestInit throws (Dataset.cs:107-110), and Config.LlffHold, Config.RenderPath, Config.GcEvery ("the
+ * number of steps to render an image") and Config.TestRenderInterval (TrainState.cs:52-53,63-64), read
+ * by nothing.  Here a whole view of an image-backed dataset (nof_dataset_from_images), at one of its
+ * scales, is rendered in one call: per chunk of the model's max_rays pixels (row-major from pixel 0, the
+ * last chunk ragged) the rays are generated from the pose — the bits nof_dataset_materialize writes for
+ * that view and scale, no record is stored —, go through the inference forward of
+ * nof_mipnerf_render_device (MipNerfModel.Call, MipNerfModel.cs:36-97; randomized 0, the model's
+ * white_bkgd: the images are those of nof_mipnerf_render_device on the materialised records in the same
+ * chunks, bitwise) and are written into the caller's image-shaped device buffers.  Everything is
+ * enqueued on the model's stream, with no host round trip between chunks; the chunk ray buffers are
+ * the dataset's own (a batch of nof_dataset_next stays valid and unchanged) and the model's Philox
+ * state is not advanced.  Nothing is allocated after the first call with a given max_rays.
+ *
+ * metrics != NULL (a scene built with images; view, not host_pose): level l's rgb is scored against the
+ * pyramid level the dataset keeps for (scale, view): per channel d = C - p and d * d in fp32, summed
+ * over channels, pixels and chunks in fp64 in a fixed order (no atomics: bit-identical run to run),
+ * mse[l] = sum / (3 w h), psnr[l] = MseToPsnr(mse[l]) (MipHelpers.cs:672).  flags & NOF_VIEW_SSIM: ssim =
+ * nof_image_metrics' SSIM of the last level against the same pixels (the dataset keeps the image itself
+ * when out->rgb[last] is NULL); otherwise NaN.  The call then synchronises the model's stream once, at
+ * the end; with metrics == NULL it does not synchronise.
+ *
+ * host_pose != NULL: 12 host floats (rotation row-major, then translation), a novel pose rendered with
+ * the scene's intrinsics at `scale` (what Config.RenderPath needs; the reference's own test poses,
+ * Dataset.cs:320-321, are not implemented and not built here); view is ignored, metrics must be NULL.
+ *
+ * Refused before any launch, the objects staying usable: NOF_ERR_UNSUPPORTED for a dataset that is not
+ * image-backed (resident records or streaming); NOF_ERR_INVALID_ARG for view or scale out of range,
+ * dataset and model on different devices, metrics on a scene built without images, metrics together
+ * with host_pose, unknown flag bits, and null ds, model or out. */
+typedef struct nof_view_out {            /* caller-provided device buffers, any may be NULL */
+  float* rgb[NOF_MAX_LEVELS];            /* [h_s][w_s][3] per level */
+  float* distance;                       /* [h_s][w_s], last level */
+  float* acc;                            /* [h_s][w_s], last level */
+} nof_view_out;
+typedef struct nof_view_metrics {
+  int32_t width, height, num_levels;
+  double mse[NOF_MAX_LEVELS];
+  float psnr[NOF_MAX_LEVELS];
+  float ssim;                            /* last level; NaN unless NOF_VIEW_SSIM */
+} nof_view_metrics;
+#define NOF_VIEW_SSIM 1u
+/* image-backed datasets: views, scales and the per-scale sizes (arrays of 4, 0 past num_scales);
+ * NOF_ERR_UNSUPPORTED for any other dataset */
+nof_status nof_dataset_scene_info(nof_dataset* ds, int32_t* num_views, int32_t* num_scales,
+                                  int32_t* w, int32_t* h, int32_t* has_images);
+nof_status nof_dataset_render_view(nof_dataset* ds, nof_mipnerf* model, int32_t view, const float* host_pose,
+                                   int32_t scale, uint32_t flags, const nof_view_out* out,
+                                   nof_view_metrics* metrics);
+
 /* ---- AcceleratedMLP (AcceleratedMLP.h:7-45) -------------------------------------------------- */
 /* get_output MLPcpp:214-255: encoded inputs in device memory (enc_pos [n*S][96] in the reference's
  * feature order, enc_dir [n][27] per ray, D5; any-shape networks: [n*S][6 (max_deg - min_deg)] and

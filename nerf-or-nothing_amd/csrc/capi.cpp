@@ -180,7 +180,7 @@ nof_status nof_device_checks(uint32_t* bits, int32_t clear) {
     NOF_HIP(hipDeviceSynchronize());
     const bool c = clear != 0;
     *bits = nof::check_unit_sampling(c) | nof::check_unit_mlp_fwd16(c) | nof::check_unit_mlp_bwd16(c) |
-            nof::check_unit_wgrad(c) | nof::check_unit_dataset(c);
+            nof::check_unit_wgrad(c) | nof::check_unit_dataset(c) | nof::check_unit_view(c);
 #else
     (void)clear;
     throw Error(NOF_ERR_UNSUPPORTED, "device checks are compiled only into lib/libnof_check.so (make check)");
@@ -335,6 +335,29 @@ nof_status nof_dataset_materialize(nof_dataset* ds, float* dev_records, void* st
     ARG(ds && dev_records);
     DEV(ds);
     ds->impl->materialize(dev_records, (hipStream_t)stream);
+  });
+}
+nof_status nof_dataset_scene_info(nof_dataset* ds, int32_t* num_views, int32_t* num_scales, int32_t* w, int32_t* h,
+                                  int32_t* has_images) {
+  return guard([&] {
+    ARG(ds && num_views && num_scales && w && h && has_images);
+    if (!ds->impl->image_backed())
+      throw Error(NOF_ERR_UNSUPPORTED, "scene_info needs an image-backed dataset (nof_dataset_from_images)");
+    const nof::MultiscaleLayout& L = ds->impl->layout();
+    *num_views = L.num_views;
+    *num_scales = L.num_scales;
+    for (int s = 0; s < nof::kMaxScales; ++s) {  // entries past num_scales are zero
+      w[s] = L.w[s]; h[s] = L.h[s];
+    }
+    *has_images = ds->impl->has_images() ? 1 : 0;
+  });
+}
+nof_status nof_dataset_render_view(nof_dataset* ds, nof_mipnerf* model, int32_t view, const float* host_pose,
+                                   int32_t scale, uint32_t flags, const nof_view_out* out, nof_view_metrics* metrics) {
+  return guard([&] {
+    ARG(ds && model && out);
+    KEEP_DEVICE;  // render_view selects the dataset's device once its arguments have passed
+    ds->impl->render_view(*model->impl, view, host_pose, scale, *out, metrics, flags);
   });
 }
 nof_status nof_recenter_poses(float* poses, int32_t V) {

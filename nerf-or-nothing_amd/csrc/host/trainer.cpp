@@ -3,6 +3,8 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -67,6 +69,10 @@ RayDataset::~RayDataset() {
     if (copied_[b]) (void)hipEventDestroy(copied_[b]);
   }
   if (gathered_) (void)hipEventDestroy(gathered_);
+  if (view_done_) {
+    (void)hipEventSynchronize(view_done_);
+    (void)hipEventDestroy(view_done_);
+  }
 }
 
 void RayDataset::fetch(int b, int n, uint64_t seed, uint32_t step, uint32_t ray_base) {
@@ -273,6 +279,102 @@ void RayDataset::next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hi
     NOF_HIP(hipMemcpyAsync(host_msum, msum_.p, sizeof(float), hipMemcpyDeviceToHost, st));
     NOF_HIP(hipStreamSynchronize(st));
   }
+}
+
+// ---- whole views (the test split) -----------------------------------------------------------------
+void RayDataset::reserve_view(int chunk, bool scratch_rgb) {
+  const int64_t npix0 = (int64_t)layout_.w[0] * layout_.h[0];  // the largest view
+  if (!view_done_) NOF_HIP(hipEventCreateWithFlags(&view_done_, hipEventDisableTiming));
+  if (chunk > vcap_) {
+    NOF_HIP(hipEventSynchronize(view_done_));  // the previous view may still read the buffers
+    vo_.alloc(3 * (size_t)chunk); vd_rays_.alloc(3 * (size_t)chunk);
+    vr_.alloc(chunk); vnr_.alloc(chunk); vfr_.alloc(chunk);
+    vcap_ = chunk;
+  }
+  // the store launches of a scale-0 view in chunks of `chunk` (no smaller view has more blocks)
+  const int64_t blocks = (npix0 / chunk) * nof::view_store_blocks(chunk) + nof::view_store_blocks((int)(npix0 % chunk));
+  if (blocks > vblocks_) {
+    NOF_HIP(hipEventSynchronize(view_done_));
+    vpart_.alloc((size_t)nof::kViewMaxLevels * (size_t)blocks);
+    if (!vsum_.p) vsum_.alloc(nof::kViewMaxLevels);
+    vblocks_ = (int)blocks;
+  }
+  if (scratch_rgb && !vrgb_.p) vrgb_.alloc(3 * (size_t)npix0);
+}
+
+void RayDataset::render_view(AcceleratedMipNeRF& model, int view, const float* host_pose, int scale,
+                             const nof_view_out& out, nof_view_metrics* metrics, uint32_t flags) {
+  if (!image_backed())
+    throw Error(NOF_ERR_UNSUPPORTED, "render_view needs an image-backed dataset (nof_dataset_from_images)");
+  NOF_REQUIRE((flags & ~(uint32_t)NOF_VIEW_SSIM) == 0, "unknown flag bits");
+  NOF_REQUIRE(scale >= 0 && scale < layout_.num_scales, "scale out of range");
+  NOF_REQUIRE(host_pose || (view >= 0 && view < layout_.num_views), "view out of range");
+  NOF_REQUIRE(model.device() == device_, "the dataset and the model are on different devices");
+  NOF_REQUIRE(!(metrics && host_pose), "a novel pose has no ground truth to score against");
+  NOF_REQUIRE(!metrics || has_images(), "the scene was built without images: nothing to score against");
+  const int w = layout_.w[scale], h = layout_.h[scale];
+  NOF_REQUIRE((int64_t)layout_.w[0] * layout_.h[0] <= 0x7FFFFFFFll, "view too large");
+  const int npix = w * h;
+  const nof_config& c = model.config();
+  const int chunk = c.max_rays, L = c.num_levels;
+  hipStream_t st = model.mlp->stream();
+  const bool ssim = metrics && (flags & NOF_VIEW_SSIM);
+  NOF_HIP(hipSetDevice(device_));
+  reserve_view(chunk, ssim && !out.rgb[L - 1]);
+  NOF_HIP(hipStreamWaitEvent(st, view_done_, 0));  // an earlier view on another stream has left the buffers
+
+  if (host_pose) view = 0;
+  const float* gt = metrics ? pyr_.p + 3 * (layout_.first[scale] + (int64_t)view * npix) : nullptr;
+  nof::ViewRayArgs ra{};
+  ra.poses = poses_.p;
+  if (host_pose) std::memcpy(ra.pose, host_pose, sizeof(ra.pose));
+  ra.use_pose = host_pose ? 1 : 0;
+  ra.view = view; ra.num_views = layout_.num_views;
+  ra.w = w; ra.h = h; ra.focal = layout_.focal[scale]; ra.near = near_; ra.far = far_; ra.ndc = ndc_;
+  ra.o = vo_.p; ra.d = vd_rays_.p; ra.radius = vr_.p; ra.nears = vnr_.p; ra.fars = vfr_.p;
+  nof::ViewStoreArgs sa{};
+  sa.num_levels = L;
+  for (int l = 0; l < L; ++l) sa.rgb[l] = out.rgb[l];
+  if (ssim && !sa.rgb[L - 1]) sa.rgb[L - 1] = vrgb_.p;
+  sa.distance = out.distance; sa.acc = out.acc;
+  sa.gt = gt;
+  sa.partials = metrics ? vpart_.p : nullptr;
+  sa.blocks = (npix / chunk) * nof::view_store_blocks(chunk) + nof::view_store_blocks(npix % chunk);
+  sa.npix = npix; sa.view = view; sa.num_views = layout_.num_views;
+  for (int p0 = 0; p0 < npix; p0 += chunk) {
+    const int n = std::min(chunk, npix - p0);
+    ra.p0 = p0; ra.n = n;
+    NOF_HIP(nof::launch_view_rays(ra, st));
+    nof_render_out ro{};
+    model.Render(n, vo_.p, vd_rays_.p, vr_.p, vnr_.p, vfr_.p, /*randomized=*/0, c.white_bkgd, &ro);
+    for (int l = 0; l < L; ++l) sa.comp_rgb[l] = ro.comp_rgb[l];
+    sa.dist_in = ro.distance[L - 1]; sa.acc_in = ro.acc[L - 1];
+    sa.p0 = p0; sa.n = n;
+    NOF_HIP(nof::launch_view_store(sa, st));
+    sa.block0 += nof::view_store_blocks(n);
+  }
+  if (!metrics) {
+    NOF_HIP(hipEventRecord(view_done_, st));
+    return;
+  }
+  double sums[nof::kViewMaxLevels] = {};
+  NOF_HIP(nof::launch_view_final(vpart_.p, sa.blocks, L, vsum_.p, st));
+  NOF_HIP(hipMemcpyAsync(sums, vsum_.p, sizeof(double) * L, hipMemcpyDeviceToHost, st));
+  float s = std::nanf("");
+  if (ssim) {  // the existing metrics launches on the assembled image; they end with the call's one synchronisation
+    float psnr_last = 0.0f;
+    NOF_HIP(nof::image_metrics(sa.rgb[L - 1], gt, w, h, 1.0f, &psnr_last, &s, st));
+  } else {
+    NOF_HIP(hipStreamSynchronize(st));
+  }
+  NOF_HIP(hipEventRecord(view_done_, st));
+  *metrics = nof_view_metrics{};
+  metrics->width = w; metrics->height = h; metrics->num_levels = L;
+  for (int l = 0; l < L; ++l) {
+    metrics->mse[l] = sums[l] / (3.0 * (double)npix);
+    metrics->psnr[l] = (float)(-10.0 / std::log(10.0) * std::log(metrics->mse[l]));  // MseToPsnr, as metrics.hip
+  }
+  metrics->ssim = s;
 }
 
 // ---- checkpoints ----------------------------------------------------------------------------------

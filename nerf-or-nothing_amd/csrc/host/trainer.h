@@ -52,9 +52,20 @@ class RayDataset {
   // Gather n records for (seed, step, first global ray id); device SoA views owned by the dataset
   // (valid until the next call).  host_msum != null: also the loss-multiplier sum (synchronises st).
   void next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hipStream_t st, nof_batch* out, float* host_msum);
+  // image-backed: the scene's shape (the layout's rows) and whether it keeps an image pyramid
+  const nof::MultiscaleLayout& layout() const { return layout_; }
+  bool has_images() const { return pyr_.p != nullptr; }
+  // A whole view (or, host_pose != null, a novel pose: 12 floats) at `scale`, rendered by `model` on its
+  // stream in chunks of its max_rays from pixel 0: per chunk the ray generator, model.Render (randomized 0,
+  // the model's white_bkgd), then the store-and-score launch (view.hip).  metrics == null: no
+  // synchronisation; else one, at the end.  Arguments are refused before any launch (include/nof.h
+  // nof_dataset_render_view).  The chunk rays are buffers of their own: next()'s batch stays as it is.
+  void render_view(AcceleratedMipNeRF& model, int view, const float* host_pose, int scale, const nof_view_out& out,
+                   nof_view_metrics* metrics, uint32_t flags);
 
  private:
   void reserve(int n, hipStream_t st);
+  void reserve_view(int chunk, bool scratch_rgb);
   // streaming: fetch the records of (seed, step, ray_base, n) into pinned buffer b
   void fetch(int b, int n, uint64_t seed, uint32_t step, uint32_t ray_base);
   int device_;
@@ -87,6 +98,13 @@ class RayDataset {
   int cap_ = 0;
   DevBuf<float> o_, d_, vd_, r_, nr_, fr_, lm_, pix_, msum_;
   DevBuf<int> idx_;
+  // render_view's state: the chunk's rays, the score's per-block partials ([levels][blocks of a scale-0
+  // view]) and sums, the last level's image when SSIM is asked for and the caller keeps none, and the event
+  // after the last call's work (a call on another stream waits for it before it reuses the buffers)
+  int vcap_ = 0, vblocks_ = 0;
+  DevBuf<float> vo_, vd_rays_, vr_, vnr_, vfr_, vrgb_;
+  DevBuf<double> vpart_, vsum_;
+  hipEvent_t view_done_ = nullptr;
 };
 
 // Dataset.GenerateRays (+ the LLFF NDC override) on the device: poses (host, V x [R row-major | t]),

@@ -14,6 +14,7 @@ uint32_t check_unit_mlp_fwd16(bool clear);
 uint32_t check_unit_mlp_bwd16(bool clear);
 uint32_t check_unit_wgrad(bool clear);
 uint32_t check_unit_dataset(bool clear);
+uint32_t check_unit_view(bool clear);
 hipError_t launch_check_selftest(hipStream_t st);  // fails kChkSelfTest on purpose
 
 // ---- sampling.hip (get_sample_t_vals AF:222-242, get_resampled_t_vals AF:246-291) ----------
@@ -297,6 +298,42 @@ hipError_t launch_gather_rays(const float* poses, const float* pyr, const Multis
                               int ndc, int n, uint64_t seed, uint32_t step, uint32_t ray_base, float* o, float* d,
                               float* vd, float* radius, float* nears, float* fars, float* lm, float* pix, int* idx_out,
                               float* lm_sum, hipStream_t st);
+
+// ---- view.hip: a whole view of an image-backed scene, chunk by chunk (include/nof.h nof_dataset_render_view) ----
+// The rays of pixels [p0, p0 + n) of a w x h view (one scale's row of the MultiscaleLayout), row-major, into a
+// device SoA; the pose is row `view` of the device table `poses`, or `pose` when use_pose.  Bit-identical to
+// launch_materialize's records of that view and scale.
+struct ViewRayArgs {
+  const float* poses;
+  float pose[12];
+  int use_pose, view, num_views;
+  int w, h;
+  float focal, near, far;
+  int ndc, p0, n;
+  float *o, *d, *radius, *nears, *fars;
+};
+hipError_t launch_view_rays(const ViewRayArgs& a, hipStream_t st);
+// A rendered chunk (comp_rgb per level, the last level's distance and acc: n rays) into image buffers at pixel
+// p0 (null ones skipped) and, gt != nullptr, each level's squared error against gt (the view's [npix][3]
+// pixels): block b of this launch writes partials[l * blocks + block0 + b], a view's launches covering
+// [0, blocks) between them.  launch_view_final then adds each level's partials in a fixed order.
+constexpr int kViewMaxLevels = 4;  // NOF_MAX_LEVELS
+constexpr int kViewStoreBlock = 256;
+inline int view_store_blocks(int n) { return (n + kViewStoreBlock - 1) / kViewStoreBlock; }
+struct ViewStoreArgs {
+  int num_levels;
+  const float* comp_rgb[kViewMaxLevels];
+  const float *dist_in, *acc_in;
+  float* rgb[kViewMaxLevels];
+  float *distance, *acc;
+  const float* gt;
+  double* partials;
+  int block0, blocks;
+  int p0, n, npix;
+  int view, num_views;
+};
+hipError_t launch_view_store(const ViewStoreArgs& a, hipStream_t st);
+hipError_t launch_view_final(const double* partials, int blocks, int num_levels, double* sums, hipStream_t st);
 
 // ---- metrics.hip: PSNR / SSIM of device images [H][W][3] (synchronises st) ----
 hipError_t image_metrics(const float* a, const float* b, int W, int H, float max_val, float* psnr, float* ssim,

@@ -68,6 +68,17 @@ class nof_step_stats(C.Structure):
                                          "clip_scale")] + [("iteration", C.c_int32)]
 
 
+class nof_view_out(C.Structure):
+    _fields_ = [("rgb", C.c_void_p * NOF_MAX_LEVELS), ("distance", C.c_void_p), ("acc", C.c_void_p)]
+
+
+class nof_view_metrics(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("num_levels", C.c_int32),
+                ("mse", C.c_double * NOF_MAX_LEVELS), ("psnr", C.c_float * NOF_MAX_LEVELS), ("ssim", C.c_float)]
+
+
+NOF_VIEW_SSIM = 1
+
 OUTPUT_GRAD_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_float, C.c_uint64)
 GRAD_BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 NOF_GRAD_ACCUMULATE, NOF_GRAD_PUBLISH, NOF_GRAD_BUCKETS = 1, 2, 2
@@ -118,6 +129,8 @@ SIGNATURES = {
                               C.POINTER(F), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "nof_dataset_from_images": [P, I32, I32, I32, F, F, F, I32, P, I32, I32, I32, C.POINTER(P)],
     "nof_dataset_materialize": [P, P, P],
+    "nof_dataset_scene_info": [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)],
+    "nof_dataset_render_view": [P, P, I32, P, I32, U32, C.POINTER(nof_view_out), C.POINTER(nof_view_metrics)],
     "nof_recenter_poses": [P, I32],
     "nof_dp_unique_id": [P],
     "nof_dp_init_rank": [P, I32, I32, I32, C.POINTER(P)],

@@ -530,6 +530,58 @@ class RayDataset:
         torch.cuda.synchronize(self._device)
         return out
 
+    def scene_info(self) -> dict:
+        """An image-backed dataset's shape: num_views, num_scales, width / height per scale, has_images
+        (any other dataset raises NofError(NOF_ERR_UNSUPPORTED))."""
+        V, S, has = C.c_int32(), C.c_int32(), C.c_int32()
+        w, h = (C.c_int32 * 4)(), (C.c_int32 * 4)()
+        call("nof_dataset_scene_info", self._h, C.byref(V), C.byref(S), w, h, C.byref(has))
+        return dict(num_views=V.value, num_scales=S.value, width=list(w[: S.value]), height=list(h[: S.value]),
+                    has_images=bool(has.value))
+
+    def render_view(self, model: "AcceleratedMipNeRF", view=None, pose=None, scale: int = 0, ssim: bool = True,
+                    score=None, outputs=None) -> dict:
+        """One whole view at `scale`, rendered on the device in chunks of the model's max_rays (include/nof.h
+        nof_dataset_render_view): view = a view of the scene, or pose = 12 floats (rotation row-major, then
+        translation) for a novel one.  Returns torch device tensors {"rgb": [per level [H, W, 3]],
+        "distance": [H, W], "acc": [H, W]} (last level), enqueued on the model's stream; outputs: None = all of
+        them, else the names to produce among "rgb" (every level), "rgb<level>", "distance", "acc" (the others
+        are None).  score (default: a view of a scene with images) adds "mse", "psnr" (per level against the
+        image the dataset keeps) and "ssim" (last level; None unless ssim), and synchronises."""
+        import torch
+
+        if (view is None) == (pose is None):
+            raise ValueError("render_view takes a view or a pose")
+        info = self.scene_info()
+        if score is None:
+            score = pose is None and info["has_images"]
+        ok = 0 <= scale < info["num_scales"]  # a scale out of range: empty buffers, the library refuses the call
+        W, H, L_ = info["width"][scale] if ok else 0, info["height"][scale] if ok else 0, model.config.num_levels
+        dev = torch.device("cuda", self._device)
+        want = None if outputs is None else set(outputs)
+
+        def buf(name, shape, level=None):
+            if want is not None and name not in want and (level is None or f"{name}{level}" not in want):
+                return None
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        res = {"rgb": [buf("rgb", (H, W, 3), l) for l in range(L_)], "distance": buf("distance", (H, W)),
+               "acc": buf("acc", (H, W)), "width": W, "height": H}
+        out = L.nof_view_out()
+        for l, t in enumerate(res["rgb"]):
+            out.rgb[l] = _ptr(t) or None
+        out.distance, out.acc = _ptr(res["distance"]) or None, _ptr(res["acc"]) or None
+        host_pose = None
+        if pose is not None:
+            host_pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(12)
+        m = L.nof_view_metrics()
+        call("nof_dataset_render_view", self._h, model._h, -1 if view is None else int(view),
+             host_pose.ctypes.data if host_pose is not None else None, int(scale),
+             L.NOF_VIEW_SSIM if (score and ssim) else 0, C.byref(out), C.byref(m) if score else None)
+        if score:
+            res.update(mse=list(m.mse[:L_]), psnr=list(m.psnr[:L_]), ssim=m.ssim if ssim else None)
+        return res
+
     def close(self):
         if getattr(self, "_h", None):
             lib().nof_dataset_destroy(self._h)

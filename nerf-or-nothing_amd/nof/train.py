@@ -5,6 +5,8 @@ never implements.
     python -m nof.train --records train_data.bin --steps 1000 [--ckpt-dir ck --save-every 500 --resume]
     python -m nof.train --synthetic 100000 --steps 200          (Lego-shaped synthetic records)
     python -m nof.train --scene scene.npz --num-scales 4        (poses + images, rays made per batch)
+    python -m nof.train --scene scene.npz --holdout 8 --eval-every 10000 [--eval-dir renders]
+                                                                (every 8th view held out, rendered and scored)
 
 One step = dataset batch (device gather) -> AcceleratedMipNeRF.get_gradient_device (fused loss
 gradient) -> [all-reduce of the gradient arena when torch.distributed is initialised] ->
@@ -139,25 +141,81 @@ class Trainer:
             self.step()
         return self
 
+    # --- the test split ---------------------------------------------------------------------------
+    def evaluate(self, test_dataset: api.RayDataset, ssim: bool = True, eval_dir: str | None = None) -> list[dict]:
+        """Every view of an image-backed test dataset at every scale, rendered and scored on the device
+        (RayDataset.render_view).  Per scale: the mean over the views of the per-view PSNR of the last and of
+        the coarse level (a mean of PSNRs, as mip-NeRF reports it) and of the SSIM (None without ssim), with
+        the per-view figures.  eval_dir: each view's rgb (last level), distance and acc as float32 .npy
+        files.  Leaves the training state (parameters, Adam, Philox state) as it is."""
+        info = test_dataset.scene_info()
+        if eval_dir:
+            os.makedirs(eval_dir, exist_ok=True)
+        last = self.cfg.num_levels - 1
+        out = []
+        for s in range(info["num_scales"]):
+            views = []
+            for v in range(info["num_views"]):
+                names = None if eval_dir else ()
+                r = test_dataset.render_view(self.model, view=v, scale=s, ssim=ssim, score=True, outputs=names)
+                views.append(dict(psnr=r["psnr"][last], psnr_coarse=r["psnr"][0], ssim=r["ssim"]))
+                if eval_dir:  # scored: the stream is synchronised
+                    stem = os.path.join(eval_dir, f"step{self.step_idx:08d}_scale{s}_view{v:03d}_")
+                    for name, t in (("rgb", r["rgb"][last]), ("distance", r["distance"]), ("acc", r["acc"])):
+                        np.save(stem + name + ".npy", t.cpu().numpy())
+            out.append(dict(scale=s, width=info["width"][s], height=info["height"][s], views=views,
+                            psnr=float(np.mean([x["psnr"] for x in views])),
+                            psnr_coarse=float(np.mean([x["psnr_coarse"] for x in views])),
+                            ssim=float(np.mean([x["ssim"] for x in views])) if ssim else None))
+        return out
 
-def scene_dataset(path, num_scales=1, multiscale_loss=True, device=0) -> api.RayDataset:
+
+def holdout_views(num_views: int, holdout: int, split: str = "train") -> list[int]:
+    """Config.LlffHold (TrainState.cs:53): with holdout = N > 0 every N-th view (i % N == 0) is the test
+    split and the rest the train split; N = 0: no test split, every view trains.  N = 1 would leave nothing
+    to train on and is refused."""
+    if split not in ("train", "test"):
+        raise ValueError(f"split must be 'train' or 'test', not {split!r}")
+    V, N = int(num_views), int(holdout)
+    if V <= 0 or N < 0:
+        raise ValueError("holdout_views needs num_views > 0 and holdout >= 0")
+    if N == 1:
+        raise ValueError("holdout 1 puts every view into the test split: nothing is left to train on")
+    test = [i for i in range(V) if N > 0 and i % N == 0]
+    return test if split == "test" else [i for i in range(V) if not (N > 0 and i % N == 0)]
+
+
+def scene_dataset(path, num_scales=1, multiscale_loss=True, device=0, holdout=0, split="train") -> api.RayDataset:
     """The image-backed dataset of a scene file (.npz: poses [V,12], images [V,H,W,3], focal, near, far,
-    optional ndc)."""
+    optional ndc).  holdout = N > 0: only the views of `split` (holdout_views), chosen on the host."""
     import torch
 
     z = np.load(path)
-    images = torch.from_numpy(np.ascontiguousarray(z["images"], dtype=np.float32)).to(torch.device("cuda", device))
+    poses = np.asarray(z["poses"], dtype=np.float32)
+    assert poses.size == z["images"].shape[0] * 12, "poses must be [V, 12] for images [V, H, W, 3]"
+    keep = holdout_views(z["images"].shape[0], holdout, split)
+    if not keep:
+        raise ValueError(f"the {split} split of {path} is empty (holdout {holdout})")
+    images = np.ascontiguousarray(z["images"][keep], dtype=np.float32)
+    images = torch.from_numpy(images).to(torch.device("cuda", device))
     V, H, W, _ = images.shape
-    assert z["poses"].size == V * 12, "poses must be [V, 12] for images [V, H, W, 3]"
     return api.RayDataset(device=device, scene=dict(
-        poses=z["poses"], width=W, height=H, focal=float(z["focal"]), near=float(z["near"]), far=float(z["far"]),
-        ndc=bool(z["ndc"]) if "ndc" in z else False, images=images, num_scales=num_scales,
+        poses=poses.reshape(-1, 12)[keep], width=W, height=H, focal=float(z["focal"]), near=float(z["near"]),
+        far=float(z["far"]), ndc=bool(z["ndc"]) if "ndc" in z else False, images=images, num_scales=num_scales,
         multiscale_loss=multiscale_loss))
 
 
-def main(argv=None):
-    from . import synth
+def format_eval(step: int, results: list[dict]) -> list[str]:
+    """one line per scale of Trainer.evaluate's results"""
+    lines = []
+    for r in results:
+        ssim = "n/a" if r["ssim"] is None else f"{r['ssim']:.6f}"
+        lines.append(f"Eval step {step}: scale {r['scale']} ({r['width']}x{r['height']}, {len(r['views'])} views) "
+                     f"PSNR {r['psnr']:.4f} dB, coarse PSNR {r['psnr_coarse']:.4f} dB, SSIM {ssim}")
+    return lines
 
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--records", help="BinDataset file of 64-byte records")
@@ -194,7 +252,29 @@ def main(argv=None):
     ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="weight_decay_mult of the loss term sum p^2 / P")
     ap.add_argument("--stats", action="store_true", help="print the gradient statistics with the loss")
+    # the test split (Config.LlffHold / GcEvery, TrainState.cs:53,63): held-out views rendered and scored on the device
+    ap.add_argument("--holdout", type=int, default=0, metavar="N",
+                    help="--scene: hold out every N-th view (i %% N == 0) as the test split; evaluated at the end")
+    ap.add_argument("--eval-every", type=int, default=0, metavar="K",
+                    help="with --holdout: also evaluate the test split every K steps")
+    ap.add_argument("--eval-dir", metavar="DIR",
+                    help="with --holdout: write each rendered test view's rgb, distance and acc as .npy files")
     a = ap.parse_args(argv)
+    if a.holdout < 0 or a.holdout == 1:
+        ap.error("--holdout must be 0 (off) or at least 2: every N-th view is held out, so 1 leaves nothing to train on")
+    if a.eval_every < 0:
+        ap.error("--eval-every must not be negative")
+    if a.holdout and not a.scene:
+        ap.error("--holdout needs --scene: only a scene of poses and images has views to hold out")
+    if (a.eval_every or a.eval_dir) and not a.holdout:
+        ap.error("--eval-every and --eval-dir need --holdout N: without held-out views there is nothing to evaluate")
+    return a
+
+
+def main(argv=None):
+    from . import synth
+
+    a = parse_args(argv)
     net = {k: getattr(a, k) for k in ("net_depth", "net_width", "net_depth_condition", "net_width_condition")
            if getattr(a, k) is not None}
     if a.samples:
@@ -202,7 +282,7 @@ def main(argv=None):
     net.update(lindisp=int(a.lindisp), ray_shape=int(a.cylinder), density_bias=a.density_bias,
                rgb_padding=a.rgb_padding)
     if a.scene:
-        ds = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device)
+        ds = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device, holdout=a.holdout)
     elif a.records:
         ds = api.RayDataset(a.records, device=a.device)
     else:
@@ -214,8 +294,27 @@ def main(argv=None):
                  precision={"f32": 0, "split": 1, "f16x2": 2, "f16split": 3, "f16": 4}[a.precision], **net)
     if a.resume:
         tr.resume(a.resume)
+    test = None
+    if a.holdout:
+        test = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device, holdout=a.holdout,
+                             split="test")
+
+    def evaluate():
+        for line in format_eval(tr.step_idx, tr.evaluate(test, eval_dir=a.eval_dir)):
+            print(line, flush=True)
+
     t0 = time.perf_counter()
-    tr.train(a.steps)
+    if test is not None and a.eval_every:
+        for _ in range(a.steps):
+            tr.step()
+            if tr.step_idx % a.eval_every == 0:
+                evaluate()
+        if tr.step_idx % a.eval_every != 0:
+            evaluate()
+    else:
+        tr.train(a.steps)
+        if test is not None:
+            evaluate()
     import torch
 
     torch.cuda.synchronize()
