@@ -8,7 +8,7 @@
 //     cost-balanced list of (problem, k-block range) items, so 256 CUs finish together;
 //   * each item accumulates a full up-to-256x256 tile in MFMA registers (8 waves x 8 tiles of
 //     32x32) over its k-blocks, staging the A (delta) and B (x) blocks with LDS-DMA into a
-//     double-buffered LDS ring, and writes one fp32 partial slab (+ bias partial);
+//     four-stage LDS ring of 16-sample half blocks, and writes one fp32 partial slab (+ bias partial);
 //   * a second launch sums the slabs of each problem in fixed order (deterministic, no atomics)
 //     into the canonical gradient arena, overwriting (level 0) or accumulating (level >= 1).
 #include "common.h"
@@ -19,16 +19,38 @@
 namespace nof {
 
 constexpr int kWgThreads = 512;       // 8 waves
-// LDS image of a staged operand: 8-row (1-KB) DMA pieces placed so that piece G starts 128 B past a
-// 256-B boundary when G & 2 (+ 256 B of padding per 4 pieces to make room).  A ds_read_b128 lane group
-// ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same +32) reads rows from all four 8-row pieces of a
-// 32-row tile; with the chunk XOR alone rows r and r + 8 share banks (2-way on every operand read),
-// with the 128-B shift of pieces 2 and 3 every group covers the 16 bank slots once.
-__host__ __device__ constexpr int wg_piece_off(int g) { return g * 8 * kBlk + 64 * (g >> 2) + 32 * ((g >> 1) & 1); }
-constexpr int kWgHalf = wg_piece_off(32);  // floats per staged operand image (max 256 rows): 34 KB
-__device__ __forceinline__ int wg_row_off(int row) { return wg_piece_off(row >> 3) + (row & 7) * kBlk; }
+// The LDS ring: kWgStages stages, a stage = the 16-sample half (64 B) of every operand row of a block,
+// laid out [A | B][stage][row][4 chunks of 16 B] (A stages first, so that a stage's byte offset fits the
+// ds_read immediate; the B half's 64 KB rides in the lane offsets).  A DMA piece is 16 rows x 64 B = 1 KB
+// (lane l: row l >> 2, position l & 3).  Row r keeps the stage's logical chunk lc (samples 4 lc .. + 3 of
+// the half) at position lc ^ ((r >> 2) & 3): the lane picks its SOURCE chunk so, the LDS image stays
+// lane-linear.  A ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same +32)
+// reads one chunk of 16 rows x of a 32-row tile, 64 B apart, so rows with equal x & 3 share a 256-B
+// bank phase; their (x >> 2) & 3 are {0,3,1,2} in the first group and {1,2,0,3} in the second, so with
+// the XOR every group covers the 16 bank slots once.
+constexpr int kWgStages = 4;
+constexpr int kWgStageOp = 256 * 16;                   // floats per operand per stage (max 256 rows): 16 KB
+constexpr int kWgLds = 2 * kWgStages * kWgStageOp;     // floats: 128 KB
+static_assert((kWgStages - 1) * kWgStageOp * 4 < 65536, "A stage offsets are ds_read immediates");
 
 typedef __attribute__((address_space(3))) void* wg_lptr_t;
+
+// s_waitcnt vmcnt(n) alone (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+}
+// End of a ring stage: this wave's LDS-DMA steps but the newest N have landed, then a bare workgroup
+// barrier (__syncthreads' fence would wait for every DMA in flight).  LDS reads in flight are not waited
+// for: their results are consumed before the wave's next barrier.  The scheduling barriers keep the
+// stage's MFMAs (register-only, free to move past an asm statement otherwise) on their side: every
+// MFMA that consumes a fragment of the stage retires its read before the barrier frees the slot.
+template <int N> __device__ __forceinline__ void wg_stage_end() {
+  static_assert(N >= 0 && N < 16, "vmcnt immediate");
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
 
 // fp32 wave-grid shapes (8 waves as (8 / GC) rows x GC columns, RB x CB 32x32 tiles per wave).
 // Wave w runs on SIMD w % 4, so a shape's cost is the MFMA time of its busiest SIMD (waves s and
@@ -41,8 +63,18 @@ constexpr int kWgNumShapes = sizeof(kWgShapes) / sizeof(kWgShapes[0]);
 // One work item (problem P, k-blocks [kb0, kb1)) for a wave grid of GR = 8 / GC rows x GC cols: wave
 // (wr, wc) owns row tiles [wr*RB, wr*RB+RB) x col tiles [wc*CB, wc*CB+CB) of the problem's tile
 // grid, so 4 k-steps cost RB + CB conflict-free ds_read_b128 for 4*RB*CB MFMAs.  Operand reads are
-// unconditional (rows/cols clamped into range) and issued one k-step ahead; the MFMAs carry no
+// unconditional (rows/cols clamped into range) and issued one k-step group ahead; the MFMAs carry no
 // branches.  Tiles outside the problem are computed on clamped duplicates and never stored.
+// Ring protocol (stage s = 16 samples = two groups of 4 k-steps, slot s % 4; E(s) = wg_stage_end at the
+// end of stage s):
+//   * the DMA of stage s + 3 is issued under the first group's MFMAs of stage s, into the slot of stage
+//     s - 1, whose last read every wave consumed before E(s - 1);
+//   * E(s) waits for all of this wave's DMA steps but the NJ of stage s + 3, i.e. for its part of stage
+//     s + 2, which the barrier then proves for every wave; stage s + 1 was proven by E(s - 1);
+//   * so the second group of stage s already reads the first fragments of stage s + 1, and a wave leaves
+//     E(s) with its operands in registers: no wave waits for LDS behind a barrier.
+// Every accumulator sees its k-steps in the order 8 cc + 4 h + i of block after block, whatever the
+// stage cut: the sums are those of a whole-block double buffer, bit for bit.
 // The waves of a grid row read the same A (delta) rows, so each keeps its row tiles rotated by wc
 // and sums only its first one (row tile r0 + wc % RB) for the bias partial: one packed add per 4
 // samples instead of RB, and every row tile summed by exactly one wave (wc < RB).  ROT needs at
@@ -50,6 +82,9 @@ constexpr int kWgNumShapes = sizeof(kWgShapes) / sizeof(kWgShapes[0]);
 template <int GC, int RB, int CB, bool ROT>
 __device__ __forceinline__ void wg_item(const WgItem& item, const WgProblem& P, float* lds, int tid, int lane,
                                         int wave, float* slabs, float* bias_slabs, const int64_t* slab_off) {
+  // opaque wave index (scalar): the wave-derived constants of the six instantiations are recomputed
+  // per item instead of being hoisted to the kernel entry all at once (they would spill)
+  asm volatile("" : "+s"(wave));
   const int h = lane >> 5, x = lane & 31;
   const int wr = wave / GC, wc = wave % GC;
   const int r0 = wr * RB, c0 = wc * CB;
@@ -59,10 +94,6 @@ __device__ __forceinline__ void wg_item(const WgItem& item, const WgProblem& P, 
   for (int r = 0; r < RB; ++r) rowt[r] = min(r0 + (ROT ? (r + wc) % RB : r), P.ntr - 1);
 #pragma unroll
   for (int c = 0; c < CB; ++c) colt[c] = min(c0 + c, P.ntc - 1);
-  const float* Ab = P.A + (size_t)P.a_row0 * kBlk;
-  const float* Bb = P.B + (size_t)P.b_col0 * kBlk;
-  const size_t strideA = (size_t)P.FA * kBlk, strideB = (size_t)P.FB * kBlk;
-
   f32x16 acc[RB][CB];
   // bias partials, two sample phases: row tile rowt[0] (ROT) or all RB row tiles
   f32x2 bs[ROT ? 1 : RB];
@@ -75,84 +106,132 @@ __device__ __forceinline__ void wg_item(const WgItem& item, const WgProblem& P, 
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[r][c][e] = 0.0f;
   }
-  // per-lane LDS row offsets (row 32*t + x of a block image; chunk c of that row at c ^ (x & 7))
-  int aoff[RB], boff[CB];
+  // per-lane LDS offsets (floats) of row 32 t + x in a stage image: chunk 2 g + h of the stage's group g
+  // (samples 8 g + 4 h .. + 3 of the half) sits at position (2 g + h) ^ sw; group 1 is group 0's
+  // offset XOR 8 floats.  The B offsets carry the B half of the ring.
+  const int sw = (x >> 2) & 3;
+  const int lo0 = ((h ^ sw) & 3) << 2;
+  int aoff[2][RB], boff[2][CB];
 #pragma unroll
-  for (int r = 0; r < RB; ++r) aoff[r] = wg_row_off(rowt[r] * 32 + x);
+  for (int r = 0; r < RB; ++r) {
+    aoff[0][r] = (rowt[r] * 32 + x) * 16 + lo0;
+    aoff[1][r] = aoff[0][r] ^ 8;
+  }
 #pragma unroll
-  for (int c = 0; c < CB; ++c) boff[c] = wg_row_off(colt[c] * 32 + x);
-  const int xs = x & 7;
+  for (int c = 0; c < CB; ++c) {
+    boff[0][c] = kWgStages * kWgStageOp + (colt[c] * 32 + x) * 16 + lo0;
+    boff[1][c] = boff[0][c] ^ 8;
+  }
 
-  // Staging in DMA steps: step j moves 1-KB piece wave + 8 j of the block's [A pieces ++ B pieces]
-  // (clamped: the surplus steps of narrower problems repeat the last piece).  Inside the k loop the
-  // NJ steps of the next block ride one per MFMA group of the first two k-step groups, so no wave
-  // stalls at a burst of VMEM issues while its SIMD's MFMA pipe waits.
-  constexpr int NJ = ((8 / GC) * RB + GC * CB + 1) / 2;  // >= (pieces of the largest problem) / 8
-  const int npA = P.ntr * 4, npT = npA + P.ntc * 4;
-  // buffer_load...lds: block base in the scalar descriptor, piece in soffset, the lane's 16 B in a
-  // loop-invariant voffset (no per-lane 64-bit addresses to keep live across the MFMA stream)
-  const int wv = __builtin_amdgcn_readfirstlane(wave);
-  auto dma_step = [&](int kbn, float* buf, int j) {
-    const int p = min(wv + 8 * j, npT - 1);
+  // Staging in DMA steps: step j moves 1-KB piece wave + 8 j of the stage's [A pieces ++ B pieces]
+  // (16 rows x 64 B each; clamped: the surplus steps of narrower problems repeat the last piece).
+  // The wave's piece table is built once per item: source of the piece in the item's first block,
+  // bytes per block of its operand, LDS offset of the piece in a stage.  buffer_load...lds takes the
+  // piece's block address in the scalar descriptor and the lane's 16 B in one of two loop-invariant
+  // voffsets (the half's 4 chunks of row l >> 2, permuted as above; the odd half 64 B further in XOR order).
+  constexpr int NJ = ((8 / GC) * RB + GC * CB + 3) / 4;  // >= (pieces of the largest problem's stage) / 8
+  static_assert(NJ <= 4, "one DMA step per MFMA group of a stage's first k-step group");
+  const int npA = P.ntr * 2, npT = npA + P.ntc * 2;
+  const char* psrc[NJ];
+  uint32_t pstep[NJ];
+  int pdst[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int p = min(wave + 8 * j, npT - 1);
     const bool isA = p < npA;  // wave-uniform
     const int q = isA ? p : p - npA;
-    const float* base = isA ? Ab + (size_t)kbn * strideA : Bb + (size_t)kbn * strideB;
+    const uint32_t F = isA ? P.FA : P.FB;
+    pstep[j] = F * (kBlk * 4);
+    psrc[j] = reinterpret_cast<const char*>(isA ? P.A : P.B) + (size_t)item.kb0 * pstep[j] +
+              (size_t)(isA ? P.a_row0 : P.b_col0) * (kBlk * 4) + q * 2048;
+    pdst[j] = (isA ? 0 : kWgStages * kWgStageOp * 4) + q * 1024;
+  }
+  const int rp = lane >> 2;
+  const int voff0 = rp * (kBlk * 4) + ((((lane & 3) ^ (rp >> 2)) ^ (rp & 7)) << 4);
+  const int voff1 = voff0 ^ 64;
+  const int K = item.kb1 - item.kb0;
+  // step j of (block kb0 + blk, half) into ring slot `slot`
+  auto dma_step = [&](int j, int blk, int half, int slot) __attribute__((always_inline)) {
+    const char* src = psrc[j] + (size_t)(uint32_t)blk * pstep[j];
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (wg_lptr_t)(buf + (isA ? 0 : kWgHalf) + wg_piece_off(q)), 16,
-                                             lane * 16, q * 1024, 0, 0);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(src), (short)0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+        rsrc, (wg_lptr_t)(reinterpret_cast<char*>(lds) + pdst[j] + slot * (kWgStageOp * 4)), 16,
+        half ? voff1 : voff0, 0, 0, 0);
   };
+  // prologue: stages 0, 1 and 2 (block 1's even half; a one-block item re-stages a duplicate nobody reads)
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) dma_step(item.kb0, lds, j);
-  __syncthreads();
-  int cur = 0;
-  for (int kb = item.kb0; kb < item.kb1; ++kb) {
-    float* nxt = lds + (cur ^ 1) * 2 * kWgHalf;
-    const int kbn = min(kb + 1, item.kb1 - 1);  // the last block re-stages itself into the idle buffer
-    if (active) {
-      const float* LA = lds + cur * 2 * kWgHalf;
-      const float* LB = LA + kWgHalf;
-      // lane half h reads chunk 2cc + h (samples 8cc + 4h .. +3); MFMA i of the group then sums
-      // k = {8cc + i, 8cc + 4 + i}, the same pairing for A and B
-      f32x4 a[RB], b[CB];
+  for (int j = 0; j < NJ; ++j) dma_step(j, 0, 0, 0);
 #pragma unroll
-      for (int r = 0; r < RB; ++r) a[r] = *reinterpret_cast<const f32x4*>(LA + aoff[r] + ((h ^ xs) << 2));
+  for (int j = 0; j < NJ; ++j) dma_step(j, 0, 1, 1);
 #pragma unroll
-      for (int c = 0; c < CB; ++c) b[c] = *reinterpret_cast<const f32x4*>(LB + boff[c] + ((h ^ xs) << 2));
+  for (int j = 0; j < NJ; ++j) dma_step(j, min(1, K - 1), 0, 2);
+  wg_stage_end<NJ>();  // stages 0 and 1 landed
+  if (active) {
+    // lane half h reads chunk 2cc + h (samples 8cc + 4h .. +3); MFMA i of the group then sums
+    // k = {8cc + i, 8cc + 4 + i}, the same pairing for A and B
+    f32x4 a[RB], b[CB];
+    // group g of the stage in `slot` (static: an immediate offset)
+    auto read = [&](int slot, int g, f32x4* fa, f32x4* fb) __attribute__((always_inline)) {
+      const float* L = lds + slot * kWgStageOp;
 #pragma unroll
-      for (int cc = 0; cc < 4; ++cc) {
-        f32x4 an[RB], bn[CB];
-        if (cc < 3) {
-          const int ch = ((2 * (cc + 1) + h) ^ xs) << 2;
+      for (int r = 0; r < RB; ++r) fa[r] = *reinterpret_cast<const f32x4*>(L + aoff[g][r]);
 #pragma unroll
-          for (int r = 0; r < RB; ++r) an[r] = *reinterpret_cast<const f32x4*>(LA + aoff[r] + ch);
+      for (int c = 0; c < CB; ++c) fb[c] = *reinterpret_cast<const f32x4*>(L + boff[g][c]);
+    };
+    // one group: the next group's fragments first, then 4 k-steps of MFMAs, the NJ DMA steps of
+    // (block blk, half) -> slot dslot riding one per k-step when dslot >= 0
+    auto group = [&](int nslot, int ng, int blk, int half, int dslot) __attribute__((always_inline)) {
+      f32x4 an[RB], bn[CB];
+      read(nslot, ng, an, bn);
+      __builtin_amdgcn_sched_barrier(0);  // reads at the head of the group, a whole group ahead of their use
 #pragma unroll
-          for (int c = 0; c < CB; ++c) bn[c] = *reinterpret_cast<const f32x4*>(LB + boff[c] + ch);
-        }
+      for (int r = 0; r < (ROT ? 1 : RB); ++r) bs[r] += f32x2{a[r][0], a[r][1]} + f32x2{a[r][2], a[r][3]};
 #pragma unroll
-        for (int r = 0; r < (ROT ? 1 : RB); ++r) bs[r] += f32x2{a[r][0], a[r][1]} + f32x2{a[r][2], a[r][3]};
+      for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int r = 0; r < RB; ++r)
 #pragma unroll
-          for (int r = 0; r < RB; ++r)
-#pragma unroll
-            for (int c = 0; c < CB; ++c) acc[r][c] = mfma32(a[r][i], b[c][i], acc[r][c]);
-          if (cc * 4 + i < NJ) dma_step(kbn, nxt, cc * 4 + i);
-        }
-        if (cc < 3) {
-#pragma unroll
-          for (int r = 0; r < RB; ++r) a[r] = an[r];
-#pragma unroll
-          for (int c = 0; c < CB; ++c) b[c] = bn[c];
+          for (int c = 0; c < CB; ++c) acc[r][c] = mfma32(a[r][i], b[c][i], acc[r][c]);
+        if (dslot >= 0 && i < NJ) {
+          dma_step(i, blk, half, dslot);
+          __builtin_amdgcn_sched_barrier(0);  // one step per k-step, not a burst of VMEM issues
         }
       }
-    } else {  // idle waves still move their pieces
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) dma_step(kbn, nxt, j);
+      for (int r = 0; r < RB; ++r) a[r] = an[r];
+#pragma unroll
+      for (int c = 0; c < CB; ++c) b[c] = bn[c];
+    };
+    // block kb (relative) in slots s0, s0 + 1: its even stage stages block kb + 1's odd half, its odd
+    // stage block kb + 2's even half (past the item: clamped duplicates that nobody reads)
+    auto block = [&](int kb, int s0) __attribute__((always_inline)) {
+      group(s0, 1, min(kb + 1, K - 1), 1, (s0 + 3) & 3);
+      group(s0 + 1, 0, 0, 0, -1);
+      wg_stage_end<NJ>();
+      group(s0 + 1, 1, min(kb + 2, K - 1), 0, s0);
+      group((s0 + 2) & 3, 0, 0, 0, -1);
+      wg_stage_end<NJ>();
+    };
+    read(0, 0, a, b);
+    int kb = 0;
+    for (; kb + 2 <= K; kb += 2) {
+      block(kb, 0);
+      block(kb + 1, 2);
     }
-    __syncthreads();
-    cur ^= 1;
+    if (kb < K) block(kb, 0);
+  } else {  // idle waves still move their pieces, with the same counts
+    for (int kb = 0; kb < K; ++kb) {
+      const int s0 = (kb & 1) * 2;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) dma_step(j, min(kb + 1, K - 1), 1, (s0 + 3) & 3);
+      wg_stage_end<NJ>();
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) dma_step(j, min(kb + 2, K - 1), 0, s0);
+      wg_stage_end<NJ>();
+    }
   }
+  wait_vmcnt<0>();  // retire the clamped tail DMAs before the ring is reused
   if (active) {
     float* slab = slabs + slab_off[item.slab];
     const int ld = P.ntc * 32;
@@ -186,9 +265,10 @@ __global__ __launch_bounds__(kWgThreads, 1) void k_wgrad(const WgProblem* __rest
                                                          const int* __restrict__ item_ptr,
                                                          const int64_t* __restrict__ slab_off, float* slabs,
                                                          float* bias_slabs) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][A | B] x kWgHalf
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [A | B][kWgStages] x kWgStageOp
   NOF_WG_T0(0)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int it0 = item_ptr[blockIdx.x], it1 = item_ptr[blockIdx.x + 1];
   for (int it = it0; it < it1; ++it) {
     NOF_IT_T0(0)
@@ -513,12 +593,6 @@ __global__ __launch_bounds__(kWgX3Threads, 1) void k_wgrad_x3(const WgProblem* _
 constexpr int kWhStages = 4;
 constexpr int kWhStageHalves = 16 * 32 * kBlk;             // up to 16 tiles (8 A + 8 B) of 2 KB
 constexpr int kWhLds = kWhStages * kWhStageHalves * 2;      // bytes: 128 KB
-
-// s_waitcnt vmcnt(n) alone (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
 
 template <int RB, int CB>
 __device__ __forceinline__ void wg_item_h(const WgItem& item, const WgProblem& P, _Float16* lds, int tid, int wave,
@@ -933,6 +1007,11 @@ int wgrad_shape(int ntr, int ntc, int* cost2) {
 // tools/diag_item_time.py: 7.82 / 3.08 / 4.99 / 1.00 us per block for the (8,8) / (8,3) / (5,8) /
 // (4,1),(1,4) tile problems): the busiest SIMD's MFMA tiles, 2-5 % dearer per tile for the narrow
 // shapes (more fragment reads per MFMA), or the staging latency that bounds the 1-tile-wide problems.
+// With the four-stage ring the same problems measure 7.65 / 2.90 / 4.82 / 0.78 us (profiles/
+// r07_wgrad_items.txt; 7.45 / 2.82 / 4.70 / 0.78 on another box), i.e. 1600 / 607 / 1008 / 163 on this
+// scale against the 1600 / 630 / 1020 / 210 below.  The constants stay: the cut they produce decides which k-blocks share a slab, hence the
+// rounding of every gradient, and the two classes that moved are 8 % and 2 % of the launch, so
+// their error shifts a workgroup's end by at most 0.5 % (the ends spread 2-3 % over the XCDs anyway).
 int wgrad_block_cost(int ntr, int ntc, int* shape) {
   int c2 = 0;
   *shape = wgrad_shape(ntr, ntc, &c2);
@@ -1096,7 +1175,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const WgOut* __restrict__ 
 hipError_t launch_wgrad(const WgProblem* probs, const WgItem* items, const int* item_ptr, int num_wg,
                         const int64_t* slab_off, float* slabs, float* bias_slabs, hipStream_t st) {
   if (num_wg <= 0) return hipSuccess;
-  const size_t shm = sizeof(float) * 4 * kWgHalf;  // 136 KB of the CU's 160 KB
+  const size_t shm = sizeof(float) * kWgLds;  // 128 KB of the CU's 160 KB
   static bool attr = false;
   if (!attr) {
     const hipError_t e = hipFuncSetAttribute((const void*)k_wgrad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
