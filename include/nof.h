@@ -47,7 +47,8 @@ typedef struct nof_config {
   int32_t net_depth, net_width;           /* 8, 256.  Any network (MLP.cs:64-86; net_depth + net_depth_condition
                                              <= 14, widths <= 4096, 0 <= min_deg < max_deg <= 24, deg_view <= 24)
                                              runs; shapes other than the reference's 8x256 / 1x128 / skip 4 / PE
-                                             (0, 16), 4 run on the any-shape fp32 path: NOF_PRECISION_F32 only */
+                                             (0, 16), 4 run on the any-shape path: NOF_PRECISION_F32 or
+                                             NOF_PRECISION_F16_PRODUCTS only */
   int32_t net_depth_condition, net_width_condition; /* 1, 128 */
   int32_t skip_layer;                     /* 4 */
   int32_t min_deg_point, max_deg_point;   /* 0, 16 */
@@ -100,13 +101,26 @@ enum { NOF_RAY_CONICAL = 0, NOF_RAY_CYLINDRICAL = 1 };
  *               fp32 accumulation; fp16 blocks and single-product weight gradients.  Parity: outputs
  *               and the integrator adjoint relative L2 <= 2e-3; gradients per tensor against fp64
  *               <= 2e-3, layer 0's W0 / b0 <= 6e-3 (fp16 pre-activations may gate a ReLU the other
- *               way; measured <= 4.9e-3, W0), all <= 2e-3 with the ReLU decisions fixed. */
+ *               way; measured <= 4.9e-3, W0), all <= 2e-3 with the ReLU decisions fixed.
+ *   F16_PRODUCTS : the any-shape path's perf mode, for every network (the reference's 8x256 runs on the
+ *               any-shape path in this mode): every MLP contraction takes ONE fp16 product per term on
+ *               v_mfma_f32_16x16x32_f16.  Both operands are rounded to fp16 (RNE) when they are staged for the
+ *               MFMA, the products accumulate in fp32 in a fixed k order; activations, deltas, parameters and
+ *               gradients stay fp32 in memory (F16 stores fp16 blocks: the two differ in storage as F16X2 and
+ *               F32_F16SPLIT do).  The backward's delta operand is multiplied by a per-level power of two
+ *               inside each product (from max |dsigma|, |drgb|, read on the device) and the sums by its exact
+ *               inverse: nothing scaled is stored.  The view encoding's weight gradient over rays stays fp32.
+ *               Heads, encodings, integrator, resampler and Adam are every mode's.  Parity: outputs and the
+ *               integrator adjoint relative L2 <= 2e-3 against the fp64 oracle, gradients per tensor <= 2e-3
+ *               with the GPU's ReLU decisions adopted.  Activations above 65504 become inf and surface
+ *               through nof_mipnerf_numeric_status, as in the other fp16 modes. */
 enum {
   NOF_PRECISION_F32 = 0,
   NOF_PRECISION_F32_SPLIT = 1,
   NOF_PRECISION_F16X2 = 2,
   NOF_PRECISION_F32_F16SPLIT = 3,
-  NOF_PRECISION_F16 = 4
+  NOF_PRECISION_F16 = 4,
+  NOF_PRECISION_F16_PRODUCTS = 5
 };
 
 void nof_config_default(nof_config* cfg);
@@ -488,6 +502,12 @@ nof_status nof_mlp_debug_view(nof_mlp* m, int32_t level, nof_mlp_debug* out);
  * nof_gen_dispatch_name: i outside [0, n) is NOF_ERR_INVALID_ARG (needs no device). */
 nof_status nof_mlp_gen_dispatch(nof_mlp* m, int32_t clear, uint32_t* counts, int32_t cap, int32_t* n);
 nof_status nof_gen_dispatch_name(int32_t i, const char** name);
+/* The same pair for the fp16-product GEMMs of NOF_PRECISION_F16_PRODUCTS (k_gemm_h, a list of its own: one
+ * name per instantiation and split / unsplit pick).  In that mode the tally above keeps counting the kernels
+ * both modes share: the encoders, k_slab_sums, k_ray_sum and the one fp32 k_gemm per level (the view
+ * encoding's weight gradient).  All zero in every other mode. */
+nof_status nof_mlp_gen_dispatch_h(nof_mlp* m, int32_t clear, uint32_t* counts, int32_t cap, int32_t* n);
+nof_status nof_gen_dispatch_h_name(int32_t i, const char** name);
 
 /* ---- AcceleratedAdamOptimizer (AcceleratedAdamOptimizer.h:5-20) ------------------------------ */
 /* ctor AcceleratedAdamOptimizer.cpp:6-21 (m, v zero-initialised: D18); cfg supplies device/stream */
@@ -583,6 +603,38 @@ nof_status nof_kernel_render_grad(int32_t n, int32_t samples, const float* densi
                                   void* stream);
 nof_status nof_kernel_adam(int64_t n, float* params, const float* grads, float* m, float* v, float lr,
                            int32_t iteration, void* stream);
+
+/* One product of NOF_PRECISION_F16_PRODUCTS (k_gemm_h), for parity tests:
+ *   C[z slab_stride + i ci + j cj] = epilogue(inv_s sum_k f16(s X(i, k)) f16(Y(j, k))),  i < M, j < N,
+ * k over chunk z = [z kchunk, min((z + 1) kchunk, K1 + K2)), z < ksplit.  Element (i, k) of an operand is
+ * src1.p[(i / idiv) si + k sk] for k < K1, else src2.p[(i / idiv) si + (k - K1) sk] (idiv 0 reads as 1; K2 = 0: no
+ * second source).  Epilogue: + bias[j], ReLU, then 0 where !(G[i gi + j gj] > 0), each optional (NULL / 0).
+ * s = 2^(8 - floor(log2 amax)) with amax = the float whose bits *scale_amax holds (1 when NULL or scale_src = 0),
+ * applied to X = A (scale_src 1) or B (2), inv_s its inverse.  rowsum (optional) [z M + i] = inv_s sum_k
+ * f16(s A(i, k)).  ksplit > 1 takes K2 = 0 and G = NULL.  The caller owns every bound: all pointers are device
+ * memory covering the indices above. */
+typedef struct nof_gemm_src {
+  const float* p;
+  int64_t si, sk;
+  int32_t idiv;
+} nof_gemm_src;
+typedef struct nof_gemm_args {
+  int32_t M, N, K1, K2;
+  nof_gemm_src A1, A2, B1, B2;
+  const float* bias;
+  int32_t relu;
+  const float* G;
+  int64_t gi, gj;
+  float* C;
+  int64_t ci, cj;
+  int32_t kchunk;
+  int64_t slab_stride;
+  float* rowsum;
+  const uint32_t* scale_amax;
+  int32_t scale_src;
+  int32_t ksplit;
+} nof_gemm_args;
+nof_status nof_kernel_gemm_h(const nof_gemm_args* args, void* stream);
 
 /* ---- per-kernel timing (hipEvents on the object's stream) ----------------------------------- */
 #define NOF_NUM_TIMERS 8

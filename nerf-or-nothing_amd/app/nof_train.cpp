@@ -19,7 +19,7 @@
 // Additions the reference declares but never implements: SaveEvery checkpoints and resume
 // (Config.SaveEvery, TrainState.cs:59).  Philox replaces the reference's unseeded System.Random.
 //
-//   nof_train --records train_data.bin [--steps K] [--batch N] [--precision f32|split|f16x2|f16split|f16]
+//   nof_train --records train_data.bin [--steps K] [--batch N] [--precision f32|split|f16x2|f16split|f16|f16p]
 //             [--print-every P] [--save-every S --ckpt-dir DIR] [--resume CKPT] [--host-api]
 //             [--seed X] [--device D | --gpus N [--dp rccl|loopback] [--attach]] [--micro-batch M]
 //             [--dump-params FILE] [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]
@@ -76,7 +76,7 @@ struct Args {
 
 [[noreturn]] void usage(int code) {
   std::fprintf(code ? stderr : stdout,
-               "usage: nof_train --records FILE [--steps K] [--batch N] [--precision f32|split|f16x2|f16split|f16]\n"
+               "usage: nof_train --records FILE [--steps K] [--batch N] [--precision f32|split|f16x2|f16split|f16|f16p]\n"
                "                 [--print-every P] [--save-every S --ckpt-dir DIR] [--resume CKPT] [--host-api]\n"
                "                 [--seed X] [--device D | --gpus N [--dp rccl|loopback] [--attach]] [--micro-batch M]\n"
                "                 [--dump-params FILE] [--max-resident RECORDS]\n"
@@ -147,6 +147,7 @@ Args parse(int argc, char** argv) {
       else if (p == "f16x2") a.precision = NOF_PRECISION_F16X2;
       else if (p == "f16split") a.precision = NOF_PRECISION_F32_F16SPLIT;
       else if (p == "f16") a.precision = NOF_PRECISION_F16;
+      else if (p == "f16p") a.precision = NOF_PRECISION_F16_PRODUCTS;  // any network (the any-shape path)
       else usage(2);
     } else {
       std::fprintf(stderr, "unknown argument %s\n", k.c_str());

@@ -514,6 +514,18 @@ nof_status nof_mlp_gen_dispatch(nof_mlp* m, int32_t clear, uint32_t* counts, int
 nof_status nof_gen_dispatch_name(int32_t i, const char** name) {
   return guard([&] { ARG(name && nof::gen_variant_name(i)); *name = nof::gen_variant_name(i); });
 }
+nof_status nof_mlp_gen_dispatch_h(nof_mlp* m, int32_t clear, uint32_t* counts, int32_t cap, int32_t* n) {
+  return guard([&] {
+    ARG(m && n && cap >= 0 && (counts || cap == 0));
+    const uint32_t* c = M(m)->gen_dispatch_h();
+    for (int i = 0; i < cap && i < nof::kGhCount; ++i) counts[i] = c[i];
+    *n = nof::kGhCount;
+    if (clear) M(m)->clear_gen_dispatch_h();
+  });
+}
+nof_status nof_gen_dispatch_h_name(int32_t i, const char** name) {
+  return guard([&] { ARG(name && nof::gen_h_variant_name(i)); *name = nof::gen_h_variant_name(i); });
+}
 
 // ---- AcceleratedAdamOptimizer ---------------------------------------------------------------
 nof_status nof_adam_create(const int32_t* layer_sizes, int32_t num_layers, const nof_config* cfg, nof_adam** out) {
@@ -712,6 +724,28 @@ nof_status nof_kernel_adam(int64_t n, float* p, const float* g, float* m, float*
     const float inv1 = 1.0f / (1.0f - std::pow(0.9f, (float)it));
     const float inv2 = 1.0f / (1.0f - std::pow(0.999f, (float)it));
     NOF_HIP(nof::launch_adam(n, p, g, m, v, lr, inv1, inv2, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_gemm_h(const nof_gemm_args* g, void* stream) {
+  return guard([&] {
+    ARG(g && g->M >= 0 && g->N >= 0 && g->K1 > 0 && g->K2 >= 0 && g->kchunk > 0 && g->ksplit >= 1 && g->C);
+    ARG(g->A1.p && g->B1.p && (g->K2 == 0 || (g->A2.p && g->B2.p)) && g->scale_src >= 0 && g->scale_src <= 2);
+    ARG((int64_t)g->ksplit * g->kchunk >= (int64_t)g->K1 + g->K2 && (g->ksplit == 1 || (g->K2 == 0 && !g->G)));
+    auto src = [](const nof_gemm_src& s) {
+      nof::GemmSrc o;
+      o.p = s.p; o.si = s.si; o.sk = s.sk; o.idiv = s.idiv > 0 ? s.idiv : 1;
+      return o;
+    };
+    nof::GemmArgs a;
+    a.M = g->M; a.N = g->N; a.K1 = g->K1; a.K2 = g->K2;
+    a.A1 = src(g->A1); a.A2 = src(g->A2); a.B1 = src(g->B1); a.B2 = src(g->B2);
+    a.bias = g->bias; a.relu = g->relu;
+    a.G = g->G; a.gi = g->gi; a.gj = g->gj;
+    a.C = g->C; a.ci = g->ci; a.cj = g->cj;
+    a.kchunk = g->kchunk; a.slab_stride = g->slab_stride;
+    a.rowsum = g->rowsum;
+    a.scale_amax = g->scale_amax; a.scale_src = g->scale_src;
+    NOF_HIP(nof::launch_gemm_h(a, g->ksplit, (hipStream_t)stream));
   });
 }
 

@@ -108,15 +108,15 @@ static void check_cfg(const nof_config& c) {
   NOF_REQUIRE(c.deg_view >= 0 && c.deg_view <= 24, "deg_view must be in [0, 24]");
   NOF_REQUIRE(c.precision == NOF_PRECISION_F32 || c.precision == NOF_PRECISION_F32_SPLIT ||
                   c.precision == NOF_PRECISION_F16X2 || c.precision == NOF_PRECISION_F32_F16SPLIT ||
-                  c.precision == NOF_PRECISION_F16,
+                  c.precision == NOF_PRECISION_F16 || c.precision == NOF_PRECISION_F16_PRODUCTS,
               "unknown precision mode");
   const bool reference_net = c.net_depth == 8 && c.net_width == 256 && c.net_depth_condition == 1 &&
                              c.net_width_condition == 128 && c.skip_layer == 4 && c.min_deg_point == 0 &&
                              c.max_deg_point == 16 && c.deg_view == 4;
-  if (!reference_net && c.precision != NOF_PRECISION_F32)
+  if (!reference_net && c.precision != NOF_PRECISION_F32 && c.precision != NOF_PRECISION_F16_PRODUCTS)
     throw Error(NOF_ERR_UNSUPPORTED,
                 "networks other than the reference's 8x256 / 1x128 / skip 4 / PE 16, 4 run in NOF_PRECISION_F32 "
-                "only (the any-shape path, generic.hip)");
+                "or NOF_PRECISION_F16_PRODUCTS only (the any-shape path, generic.hip / gemm_h.hip)");
   NOF_REQUIRE(c.grad_buckets == 0 || c.grad_buckets == 1, "grad_buckets must be 0 or 1");
   NOF_REQUIRE(c.lindisp == 0 || c.lindisp == 1, "lindisp must be 0 or 1");
   NOF_REQUIRE(c.ray_shape == NOF_RAY_CONICAL || c.ray_shape == NOF_RAY_CYLINDRICAL, "unknown ray_shape");
@@ -156,8 +156,10 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
   for (int l = 0; l < L; ++l) { boff_[l] = (int)o; o += out_[l]; }
   NOF_REQUIRE(o < (size_t)1 << 31, "network too large");
   P_ = o;
+  // (F16_PRODUCTS is the any-shape path's mode: the reference network runs there too)
   generic_ = !(D == 8 && W == 256 && Dc == 1 && Wc == 128 && cfg.skip_layer == 4 && cfg.min_deg_point == 0 &&
-               cfg.max_deg_point == 16 && cfg.deg_view == 4);
+               cfg.max_deg_point == 16 && cfg.deg_view == 4) ||
+             cfg.precision == NOF_PRECISION_F16_PRODUCTS;
 
   params_.alloc(P_);
   grads_.alloc(P_);
@@ -223,7 +225,14 @@ std::vector<int> AcceleratedMLP::get_layer_sizes() const {
 }
 
 bool AcceleratedMLP::pack_weights(const nof::StratArgs* strat) {
-  if (generic_) return false;  // the any-shape path reads the canonical arena directly
+  if (generic_) {  // the any-shape path reads the canonical arena directly
+    if (f16_products()) {  // the step's delta-scale maxima start at 0
+      NOF_HIP(hipMemsetAsync(amax_.p, 0, lv_.size() * sizeof(uint32_t), st_));
+      amax_cleared_ = (1u << lv_.size()) - 1u;
+      amax_given_ = 0u;
+    }
+    return false;
+  }
   nof::PackArgs pa;
   if (strat) pa.strat = *strat;
   for (int l = 0; l < kLayers; ++l) { pa.woff[l] = woff_[l]; pa.boff[l] = boff_[l]; }
@@ -244,7 +253,7 @@ bool AcceleratedMLP::pack_weights(const nof::StratArgs* strat) {
 }
 
 uint32_t* AcceleratedMLP::claim_delta_amax(int level) {
-  if (!f16_pieces() || level < 0 || level >= (int)lv_.size() || !((amax_cleared_ >> level) & 1u)) return nullptr;
+  if (!(f16_pieces() || f16_products()) || level < 0 || level >= (int)lv_.size() || !((amax_cleared_ >> level) & 1u)) return nullptr;
   amax_cleared_ &= ~(1u << level);
   amax_given_ |= 1u << level;
   return amax_.p + level;
@@ -780,8 +789,9 @@ float* const* AcceleratedMLP::get_gradient_levels(const float* const* color_grad
 }
 
 // ------------------------------------------------------------------------------------------------
-// Any-shape fp32 path (generic.hip).  Per level: trunk activations h_l [M][W] (l < D), condition
-// activations [M][Wc] (Dc of them), heads z [M][4]; the backward walks the layers in reverse (as
+// Any-shape path (generic.hip; NOF_PRECISION_F16_PRODUCTS: the same sequence with every product but the view
+// PE's weight gradient on gemm_h.hip's fp16 products, no weight-stationary kernel and no mask bits).  Per
+// level: trunk activations h_l [M][W] (l < D), condition activations [M][Wc] (Dc of them), heads z [M][4]; the backward walks the layers in reverse (as
 // mlp_backward_sample / MLPcpp:256-321), one dX GEMM (ReLU mask = the stored activation > 0) and one
 // split-K weight-gradient GEMM + ordered slab sum per layer and input block.
 // ------------------------------------------------------------------------------------------------
@@ -795,6 +805,11 @@ void AcceleratedMLP::gemm1(nof::GemmArgs a) {  // no split: one k chunk
   a.kchunk = (a.K1 + a.K2 + 15) / 16 * 16;
   a.slab_stride = 0;
   int v;
+  if (f16_products()) {
+    NOF_HIP(nof::launch_gemm_h(a, 1, st_, &v));
+    tally_h(v);
+    return;
+  }
   NOF_HIP(nof::launch_gemm(a, 1, st_, &v));
   tally(v);
 }
@@ -836,6 +851,10 @@ void AcceleratedMLP::gen_alloc() {
   gd1_.alloc((size_t)max_M_ * Wm);
   gdz_.alloc((size_t)max_M_ * 4);
   gray_.alloc((size_t)cfg_.max_rays * gWc_);
+  if (f16_products()) {
+    amax_.alloc(NL);
+    NOF_HIP(hipMemset(amax_.p, 0, NL * sizeof(uint32_t)));
+  }
   // split-K slabs: a level's weight gradients each take their own region (their sums run at the end of the
   // level), sized by a dry run of gen_backward at every level's capacity (the split grows with M up to its
   // tile-count cap, so the capacity bounds every call): the same call sequence as a step, so a new layer
@@ -855,7 +874,7 @@ void AcceleratedMLP::gen_alloc() {
 }
 
 void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t ldz, int nout, nof::GemmSrc x,
-                               int ncols, int M, int accumulate, float* bias_dst) {
+                               int ncols, int M, int accumulate, float* bias_dst, const uint32_t* scale) {
   int ks, kc;
   gen_split(nout, ncols, M, &ks, &kc);
   const size_t need = (size_t)ks * nout * (ncols + 1);  // + the bias partials
@@ -875,14 +894,20 @@ void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t 
   float* bias_part = slab + (size_t)ks * nout * ncols;  // the bias gradient's per-chunk sums [ks][nout]
   if (bias_dst) a.rowsum = bias_part;
   int v;
-  NOF_HIP(nof::launch_gemm(a, ks, st_, &v));
-  tally(v);
+  if (scale) {  // F16_PRODUCTS: dZ scaled inside each fp16 product, the partials unscaled
+    a.scale_amax = scale; a.scale_src = 1;
+    NOF_HIP(nof::launch_gemm_h(a, ks, st_, &v));
+    tally_h(v);
+  } else {
+    NOF_HIP(nof::launch_gemm(a, ks, st_, &v));
+    tally(v);
+  }
   wg_jobs_.push_back({slab, dst, a.slab_stride, ld, nout, ncols, ncols, ks, accumulate});
   if (bias_dst) wg_jobs_.push_back({bias_part, bias_dst, nout, nout, 1, nout, nout, ks, accumulate});
 }
 
 bool AcceleratedMLP::gen_gemm(nof::GemmArgs a) {
-  if (nof::gemm_ws_fits(a)) {
+  if (!f16_products() && nof::gemm_ws_fits(a)) {
     int v;
     NOF_HIP(nof::launch_gemm_ws(a, st_, &v));
     tally(v);
@@ -972,6 +997,8 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   float* dz = gdz_.p;
   float *cur = gd0_.p, *nxt = gd1_.p;
   auto MB = [&](int l) -> const uint32_t* { return G.mbits.p + (size_t)l * M * 4; };
+  // F16_PRODUCTS: the level's delta-scale word; every product with a delta operand scales it (null: no scale)
+  const uint32_t* sc = f16_products() ? amax_.p + level : nullptr;
   // the masking layer's ReLU: its bits where the forward wrote them (mlay: trunk l, condition D + i) and the
   // weight-stationary kernel fits the product, else the activation `mask` > 0 (k_gemm)
   auto masked = [&](nof::GemmArgs a, int mlay, const float* mask, int width) {
@@ -994,33 +1021,45 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.A1 = gsrc(dzp, ldz, 1);
     a.B1 = gsrc(prm + woff_[l], 1, in_[l]);
     a.C = C; a.ci = width; a.cj = 1;
+    if (sc) { a.scale_amax = sc; a.scale_src = 1; }
     masked(a, mlay, mask, width);
   };
   wg_jobs_.clear();
   wg_off_ = 0;
   if (!dry) {
+    if (sc) {  // the level's power-of-two delta scale (as bwd_args for the fused network)
+      if ((amax_given_ >> level) & 1u) {  // filled by the integrator adjoint (claim_delta_amax)
+        amax_given_ &= ~(1u << level);
+      } else {
+        const bool cleared = (amax_cleared_ >> level) & 1u;  // by this step's pack_weights, not used since
+        amax_cleared_ &= ~(1u << level);
+        NOF_HIP(nof::launch_delta_amax(density_grad, color_grad, M, amax_.p + level, st_, numeric_.p, cleared));
+      }
+    }
     tb(kTMlpBwd);
     NOF_HIP(nof::launch_heads_bwd(M, density_grad, color_grad, G.z.p, dz, cfg_.density_bias, rgb_scale(), st_));  // MNcs:23-28,184-189
   }
   // rgb head: dW, db from dz[:, 0..2] (k_heads_bwd: [dz_rgb, dz_sigma]); its dX into the last condition layer
-  gen_wgrad(gr + woff_[lr], Wc, dz, 4, 3, gsrc(Hc(Dc - 1), 1, Wc), Wc, M, acc, gr + boff_[lr]);
+  gen_wgrad(gr + woff_[lr], Wc, dz, 4, 3, gsrc(Hc(Dc - 1), 1, Wc), Wc, M, acc, gr + boff_[lr], sc);
   dx(dz, 4, 3, lr, D + Dc - 1, Hc(Dc - 1), Wc, cur);
   for (int i = Dc - 1; i >= 1; --i) {  // condition layers
     const int l = D + 1 + i;
-    gen_wgrad(gr + woff_[l], Wc, cur, Wc, Wc, gsrc(Hc(i - 1), 1, Wc), Wc, M, acc, gr + boff_[l]);
+    gen_wgrad(gr + woff_[l], Wc, cur, Wc, Wc, gsrc(Hc(i - 1), 1, Wc), Wc, M, acc, gr + boff_[l], sc);
     dx(cur, Wc, Wc, l, D + i - 1, Hc(i - 1), Wc, nxt);
     std::swap(cur, nxt);
   }
   // view layer: columns [0, W) against h_{D-1}, [W, W + Vd) against the ray's view PE
-  gen_wgrad(gr + woff_[D + 1], W + Vd, cur, Wc, Wc, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D + 1]);
-  // (the view PE is per ray: dW_pe = sum over rays of (sum over the ray's samples of dZ) PE(ray))
+  gen_wgrad(gr + woff_[D + 1], W + Vd, cur, Wc, Wc, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D + 1], sc);
+  // (the view PE is per ray: dW_pe = sum over rays of (sum over the ray's samples of dZ) PE(ray)).  In every
+  // mode on fp32 k_gemm: a sum over up to 512 samples does not share the head deltas' range (the scale
+  // leaves 2^7 above their maximum), and with k = rays the product's FLOPs are negligible
   if (!dry) {
     NOF_HIP(nof::launch_ray_sum(M / S, S, Wc, cur, Wc, gray_.p, st_));
     tally(nof::kGvRaySum);
   }
   gen_wgrad(gr + woff_[D + 1] + W, W + Vd, gray_.p, Wc, Wc, gsrc(G.ed, 1, Vd), Vd, M / S, acc);
   // density head
-  gen_wgrad(gr + woff_[D], W, dz + 3, 4, 1, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D]);
+  gen_wgrad(gr + woff_[D], W, dz + 3, 4, 1, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D], sc);
   if (!dry) {  // dh_{D-1} = dZ_view W_view[:, :W] + dz_density w_D (MLPcs:148-153, D11), masked
     nof::GemmArgs a;
     a.M = M; a.N = W; a.K1 = Wc; a.K2 = 1;
@@ -1029,16 +1068,17 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.B1 = gsrc(prm + woff_[D + 1], 1, W + Vd);
     a.B2 = gsrc(prm + woff_[D], 1, 0);
     a.C = nxt; a.ci = W; a.cj = 1;
+    if (sc) { a.scale_amax = sc; a.scale_src = 1; }  // (A2 = dz_density is a delta as well)
     masked(a, D - 1, H(D - 1), W);
     std::swap(cur, nxt);
   }
   for (int l = D - 1; l >= 0; --l) {  // trunk
     float* gw = gr + woff_[l];
     if (l > 0) {
-      gen_wgrad(gw, in_[l], cur, W, W, gsrc(H(l - 1), 1, W), W, M, acc, gr + boff_[l]);
-      if (l % gskip_ == 0) gen_wgrad(gw + W, in_[l], cur, W, W, gsrc(G.ep, 1, P), P, M, acc);
+      gen_wgrad(gw, in_[l], cur, W, W, gsrc(H(l - 1), 1, W), W, M, acc, gr + boff_[l], sc);
+      if (l % gskip_ == 0) gen_wgrad(gw + W, in_[l], cur, W, W, gsrc(G.ep, 1, P), P, M, acc, nullptr, sc);
     } else {
-      gen_wgrad(gw, P, cur, W, W, gsrc(G.ep, 1, P), P, M, acc, gr + boff_[l]);
+      gen_wgrad(gw, P, cur, W, W, gsrc(G.ep, 1, P), P, M, acc, gr + boff_[l], sc);
     }
     if (l > 0) {
       dx(cur, W, W, l, l - 1, H(l - 1), W, nxt);

@@ -100,8 +100,8 @@ class AcceleratedMLP {
   static constexpr int kTensors = 22;  // [W0..W10, b0..b10]
   static constexpr int kMaxLayers = 16;  // any-shape networks: D + Dc + 2 layers (2L <= 32 checkpoint sizes)
   int num_layers() const { return (int)out_.size(); }
-  // the network is not the reference's 8x256 / 1x128 / skip 4 / PE (0, 16), 4: the any-shape fp32 path
-  // (generic.hip) runs it
+  // the network is not the reference's 8x256 / 1x128 / skip 4 / PE (0, 16), 4, or the mode is
+  // NOF_PRECISION_F16_PRODUCTS: the any-shape path (generic.hip, gemm_h.hip) runs it
   bool generic() const { return generic_; }
 
   AcceleratedMLP(int deg_point, int deg_view, const nof_config& cfg);  // MLPcpp:168-213
@@ -155,6 +155,9 @@ class AcceleratedMLP {
   // counts of real launches: the slab-sizing dry run is not one; all zero for the fused networks)
   const uint32_t* gen_dispatch() const { return disp_; }
   void clear_gen_dispatch() { for (uint32_t& c : disp_) c = 0; }
+  // the same for nof::GenHVariant: the fp16-product GEMMs of NOF_PRECISION_F16_PRODUCTS (gemm_h.hip)
+  const uint32_t* gen_dispatch_h() const { return disp_h_; }
+  void clear_gen_dispatch_h() { for (uint32_t& c : disp_h_) c = 0; }
   // non-finite flags: [0] forward (set by the owner's integrator), [1] output gradients (f16x2 scaling)
   uint32_t* numeric_flags() const { return numeric_.p; }
   // The fused step's integrator adjoint takes a level's delta-scale maximum (f16 modes) from the values
@@ -204,6 +207,9 @@ class AcceleratedMLP {
     return precision_ == NOF_PRECISION_F16X2 || precision_ == NOF_PRECISION_F32_F16SPLIT || precision_ == NOF_PRECISION_F16;
   }
   // fp16 activation / delta blocks and the k_wgrad_h weight gradients (F16X2, F16)
+  // NOF_PRECISION_F16_PRODUCTS: every product of the any-shape path on k_gemm_h (one fp16 product per term,
+  // fp32 storage), the backward's delta operands power-of-2 scaled inside the products
+  bool f16_products() const { return precision_ == NOF_PRECISION_F16_PRODUCTS; }
   bool f16_blocks() const { return precision_ == NOF_PRECISION_F16X2 || precision_ == NOF_PRECISION_F16; }
   // RGB head scale (1 + 2 RgbPadding) formed in fp32 as the C# expression is (MNcs:22,151)
   float rgb_scale() const { return 1.0f + 2.0f * cfg_.rgb_padding; }
@@ -225,9 +231,11 @@ class AcceleratedMLP {
   // an unsplit product: the weight-stationary kernel where the shape fits it (gemm_ws.hip), else k_gemm;
   // returns whether the weight-stationary kernel ran
   bool gen_gemm(nof::GemmArgs a);
-  void gemm1(nof::GemmArgs a);  // k_gemm, no split: one k chunk
+  void gemm1(nof::GemmArgs a);  // k_gemm (k_gemm_h with f16_products()), no split: one k chunk
   uint32_t disp_[nof::kGvCount] = {};
+  uint32_t disp_h_[nof::kGhCount] = {};
   void tally(int variant, int launches = 1) { if (variant >= 0) disp_[variant] += (uint32_t)launches; }
+  void tally_h(int variant) { if (variant >= 0) ++disp_h_[variant]; }
   std::vector<GenLevel> gl_;
   DevBuf<float> gd0_, gd1_, gdz_, gslab_;  // dZ ping-pong [M][max(W, Wc)], heads dz [M][4], split-K partials
   DevBuf<float> gray_;                    // per-ray sums of the view layer's dZ [rays][Wc]
@@ -242,9 +250,10 @@ class AcceleratedMLP {
   std::vector<nof::SlabJob> wg_jobs_;
   size_t wg_off_ = 0;
   // a column block of a layer's weight gradient: dst[o ld + j] (+)= sum_m dZ(m, o) X(m, j); bias_dst: the
-  // layer's bias gradient sum_m dZ(m, o) too (row sums of the same A tiles)
+  // layer's bias gradient sum_m dZ(m, o) too (row sums of the same A tiles).  scale: with f16_products(), the
+  // level's delta-scale word (dZ is scaled inside each fp16 product); null keeps the product on fp32 k_gemm
   void gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t ldz, int nout, nof::GemmSrc x, int ncols, int M,
-                 int accumulate, float* bias_dst = nullptr);
+                 int accumulate, float* bias_dst = nullptr, const uint32_t* scale = nullptr);
   static void gen_split(int nout, int ncols, int M, int* ksplit, int* kchunk);
   float* const* gen_publish(bool buckets);  // the bucket hook once per bucket (every gradient is final)
   DevBuf<float> params_, grads_, wimg_f_, wimg_b_;
@@ -252,8 +261,9 @@ class AcceleratedMLP {
   std::vector<Level> lv_;
   int max_M_ = 0;
   DevBuf<float> slabs_, bias_slabs_;
-  DevBuf<uint32_t> amax_;  // f16 modes: per level, bits of max |dsigma|, |drgb| (the level's delta scale)
-  uint32_t amax_cleared_ = 0;  // levels whose amax word the last pack launch zeroed and no pass used yet
+  DevBuf<uint32_t> amax_;  // f16 modes (F16_PRODUCTS too): per level, bits of max |dsigma|, |drgb| (the level's delta scale)
+  uint32_t amax_cleared_ = 0;  // levels whose amax word the last pack launch (F16_PRODUCTS: pack_weights' memset)
+                               // zeroed and no pass used yet
   uint32_t amax_given_ = 0;    // levels whose amax word a claim_delta_amax caller fills (no k_delta_amax)
   DevBuf<uint32_t> numeric_;
   size_t slab_cap_ = 0;

@@ -204,6 +204,10 @@ struct GemmArgs {
   // written by a ReLU product (mask_out), applied by a dX product (mask_in) in place of G
   const uint32_t* mask_in = nullptr;
   uint32_t* mask_out = nullptr;
+  // gemm_h.hip only: the power-of-two scale s = delta_scale(scale_amax) (mlp_common.h; read on the device) of
+  // one operand inside each fp16 product, its inverse applied to the sums: 0 none, 1 the A operand, 2 B
+  const uint32_t* scale_amax = nullptr;
+  int scale_src = 0;
 };
 // Every kernel variant the any-shape launchers can select (AcceleratedMLP's dispatch tally: tests and
 // tooling see which instantiation a product ran on).  A launcher reports its pick through its optional
@@ -227,6 +231,19 @@ enum GenVariant : int {
 };
 const char* gen_variant_name(int v);  // null outside [0, kGvCount)
 hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st, int* variant = nullptr);
+// gemm_h.hip (NOF_PRECISION_F16_PRODUCTS): launch_gemm's product with one fp16 product per term on
+// v_mfma_f32_16x16x32_f16: C(i, j) = epilogue(inv_s sum_k f16(s X(i, k)) f16(Y(j, k))), X the operand
+// a.scale_src names, fp32 sums in a fixed k order; rowsum[z M + i] = inv_s sum_k f16(s A(i, k)).  kchunk: any
+// positive count; split-K (ksplit > 1) takes one k source and no mask.  Its own variant list (a tally of its
+// own: AcceleratedMLP::gen_dispatch_h):
+enum GenHVariant : int {
+  kGhGemm64 = 0,       // k_gemm_h<64, TWO, MASK>, one k chunk: + TWO + 2 MASK
+  kGhGemm64Split = 4,  // k_gemm_h<64, false, false>, split-K
+  kGhGemm128Split,     // k_gemm_h<128, false, false>, split-K, N > 64
+  kGhCount
+};
+const char* gen_h_variant_name(int v);  // null outside [0, kGhCount)
+hipError_t launch_gemm_h(const GemmArgs& a, int ksplit, hipStream_t st, int* variant = nullptr);
 // gemm_ws.hip: the weight-stationary form for N <= 128, 16-padded K1 + K2 <= 160, no split, no G / rowsum
 constexpr int kWsMaxN = 128, kWsMaxK = 160;
 bool gemm_ws_fits(const GemmArgs& a);

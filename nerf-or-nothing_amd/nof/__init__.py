@@ -19,10 +19,12 @@ from .api import (  # noqa: F401
     device_checks_selftest,
     device_count,
     device_tensor,
+    gen_dispatch_h_names,
     gen_dispatch_names,
     generate_rays,
     grad_bucket_spans,
     image_metrics,
+    kernel_gemm_h,
     learning_rate_decay,
     multiscale_layout,
     to_numpy,

@@ -25,6 +25,11 @@ class NofError(RuntimeError):
 
 
 NOF_PRECISION_F32, NOF_PRECISION_F32_SPLIT, NOF_PRECISION_F16X2, NOF_PRECISION_F32_F16SPLIT, NOF_PRECISION_F16 = 0, 1, 2, 3, 4
+NOF_PRECISION_F16_PRODUCTS = 5  # the any-shape path's fp16-product mode (every network)
+# the training drivers' --precision names
+PRECISION_NAMES = {"f32": NOF_PRECISION_F32, "split": NOF_PRECISION_F32_SPLIT, "f16x2": NOF_PRECISION_F16X2,
+                   "f16split": NOF_PRECISION_F32_F16SPLIT, "f16": NOF_PRECISION_F16,
+                   "f16p": NOF_PRECISION_F16_PRODUCTS}
 
 
 class nof_config(C.Structure):
@@ -51,6 +56,19 @@ class nof_mlp_debug(C.Structure):
     _fields_ = [("M", C.c_int32)] + [(k, C.c_void_p) for k in
                                      ("act_in", "act_h", "act_h9", "masks", "zhead", "delta", "delta9x")] + \
         [("generic", C.c_int32), ("gen_h", C.c_void_p), ("gen_hc", C.c_void_p)]
+
+
+class nof_gemm_src(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("si", C.c_int64), ("sk", C.c_int64), ("idiv", C.c_int32)]
+
+
+class nof_gemm_args(C.Structure):
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K1", C.c_int32), ("K2", C.c_int32),
+                ("A1", nof_gemm_src), ("A2", nof_gemm_src), ("B1", nof_gemm_src), ("B2", nof_gemm_src),
+                ("bias", C.c_void_p), ("relu", C.c_int32), ("G", C.c_void_p), ("gi", C.c_int64), ("gj", C.c_int64),
+                ("C", C.c_void_p), ("ci", C.c_int64), ("cj", C.c_int64), ("kchunk", C.c_int32),
+                ("slab_stride", C.c_int64), ("rowsum", C.c_void_p), ("scale_amax", C.c_void_p),
+                ("scale_src", C.c_int32), ("ksplit", C.c_int32)]
 
 
 class nof_render_out(C.Structure):
@@ -163,6 +181,8 @@ SIGNATURES = {
     "nof_mlp_debug_view": [P, I32, C.POINTER(nof_mlp_debug)],
     "nof_mlp_gen_dispatch": [P, I32, C.POINTER(U32), I32, C.POINTER(I32)],
     "nof_gen_dispatch_name": [I32, C.POINTER(C.c_char_p)],
+    "nof_mlp_gen_dispatch_h": [P, I32, C.POINTER(U32), I32, C.POINTER(I32)],
+    "nof_gen_dispatch_h_name": [I32, C.POINTER(C.c_char_p)],
     "nof_adam_create": [C.POINTER(I32), I32, C.POINTER(nof_config), C.POINTER(P)],
     "nof_adam_step": [P, PP, PP, F],
     "nof_adam_iteration": [P, C.POINTER(I32)],
@@ -194,6 +214,7 @@ SIGNATURES = {
     "nof_kernel_render": [I32, I32, P, P, P, P, I32, P, P, P],
     "nof_kernel_render_grad": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P],
     "nof_kernel_adam": [C.c_int64, P, P, P, P, F, I32, P],
+    "nof_kernel_gemm_h": [C.POINTER(nof_gemm_args), P],
 }
 _RESTYPE = {"nof_config_default": None, "nof_last_error": C.c_char_p, "nof_version": C.c_char_p,
             "nof_config_size": C.c_size_t,

@@ -62,6 +62,31 @@ def gen_dispatch_names() -> list[str]:
     return out
 
 
+def gen_dispatch_h_names() -> list[str]:
+    """The fp16-product GEMM variants (NOF_PRECISION_F16_PRODUCTS, k_gemm_h) in the order of their tally."""
+    out, name = [], C.c_char_p()
+    while lib().nof_gen_dispatch_h_name(len(out), C.byref(name)) == 0:
+        out.append(name.value.decode())
+    return out
+
+
+def kernel_gemm_h(stream=None, **fields) -> None:
+    """One k_gemm_h product (include/nof.h nof_kernel_gemm_h).  fields: nof_gemm_args members; A1 / A2 / B1 / B2
+    as (pointer or tensor, si, sk[, idiv]) tuples, the other pointers as device pointers or tensors."""
+    a = L.nof_gemm_args()
+    a.ksplit = 1
+    for k, v in fields.items():
+        if k in ("A1", "A2", "B1", "B2"):
+            src = getattr(a, k)
+            src.p, src.si, src.sk = _ptr(v[0]), int(v[1]), int(v[2])
+            src.idiv = int(v[3]) if len(v) > 3 else 1
+        elif k in ("bias", "G", "C", "rowsum", "scale_amax"):
+            setattr(a, k, None if v is None else _ptr(v))
+        else:
+            setattr(a, k, int(v))
+    call("nof_kernel_gemm_h", C.byref(a), stream)
+
+
 class AcceleratedMLP:
     """Borrowed view of the MLP owned by an AcceleratedMipNeRF (AcceleratedMLP.h:7-45)."""
 
@@ -122,6 +147,17 @@ class AcceleratedMLP:
         call("nof_mlp_gen_dispatch", self._h, int(bool(clear)), counts, len(names), C.byref(n))
         if n.value != len(names):
             raise RuntimeError(f"nof_mlp_gen_dispatch: {n.value} variants, {len(names)} names")
+        return {k: int(counts[i]) for i, k in enumerate(names)}
+
+    def gen_dispatch_h(self, clear: bool = False) -> dict:
+        """gen_dispatch for the fp16-product GEMMs of NOF_PRECISION_F16_PRODUCTS (name -> count; all zero in
+        every other mode)."""
+        names = gen_dispatch_h_names()
+        counts = (C.c_uint32 * len(names))()
+        n = C.c_int32()
+        call("nof_mlp_gen_dispatch_h", self._h, int(bool(clear)), counts, len(names), C.byref(n))
+        if n.value != len(names):
+            raise RuntimeError(f"nof_mlp_gen_dispatch_h: {n.value} variants, {len(names)} names")
         return {k: int(counts[i]) for i, k in enumerate(names)}
 
     def relu_masks(self, level: int) -> np.ndarray:

@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 from . import api
-from ._lib import default_config
+from ._lib import PRECISION_NAMES, default_config
 
 
 class Trainer:
@@ -228,7 +228,7 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--precision", choices=["f32", "split", "f16x2", "f16split", "f16"], default="f32")
+    ap.add_argument("--precision", choices=["f32", "split", "f16x2", "f16split", "f16", "f16p"], default="f32")
     ap.add_argument("--print-every", type=int, default=100)
     ap.add_argument("--save-every", type=int, default=0)
     ap.add_argument("--ckpt-dir")
@@ -291,7 +291,7 @@ def main(argv=None):
                  ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
                  grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
                  stats=a.stats,
-                 precision={"f32": 0, "split": 1, "f16x2": 2, "f16split": 3, "f16": 4}[a.precision], **net)
+                 precision=PRECISION_NAMES[a.precision], **net)
     if a.resume:
         tr.resume(a.resume)
     test = None
