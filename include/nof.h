@@ -74,8 +74,18 @@ typedef struct nof_config {
   float rgb_padding;                      /* MipNerfModel.RgbPadding (MNcs:22): rgb = sigmoid(z) (1 + 2 p) - p;
                                              0.001, in [0, 0.5).  The activations themselves are the
                                              reference's fixed softplus / sigmoid (MNcs:19,21) */
+  int32_t stop_level_grad;                /* MipNerfModel.StopLevelGrad (MNcs:13, declared and read by nothing): 1
+                                             (default): level l + 1's t-values are constants of the backward; 0:
+                                             t^{l+1} = resample(t^l, w^l; u) is differentiated in w^l and t^l, so
+                                             a finer level's loss trains the coarser pass as a proposal (the
+                                             discrete decisions of the resampler held at their forward values).
+                                             0 runs on the any-shape path: NOF_PRECISION_F32 (the reference 8x256
+                                             network is routed there) or NOF_PRECISION_F16_PRODUCTS; the fused
+                                             8x256 modes produce no input gradient: NOF_ERR_UNSUPPORTED.  The
+                                             forward is unchanged by the option; num_levels == 1: a no-op */
 } nof_config;
-/* The struct grows at its end only (grad_buckets, then lindisp / ray_shape, then density_bias / rgb_padding): a binding
+/* The struct grows at its end only (grad_buckets, then lindisp / ray_shape, then density_bias / rgb_padding, then
+ * stop_level_grad): a binding
  * compiled against an older header passes a shorter struct.  nof_config_size() is sizeof(nof_config) of
  * this library; a binding checks it against its own struct size before passing one. */
 size_t nof_config_size(void);
@@ -207,6 +217,11 @@ typedef struct nof_level_view {
   const float* rgb_grad;   /* [n][S][3] */
 } nof_level_view;
 nof_status nof_mipnerf_level_view(nof_mipnerf* h, int32_t level, nof_level_view* out);
+/* stop_level_grad = 0: borrowed device views of the last step's cross-level terms (tests and tooling):
+ * *w_grad = q^level [n][S] = dL/dw^level from level + 1's resampler (NULL for the last level), *t_grad =
+ * dL/dt^level [n][S + 1] = integrator + encoding + bin-edge terms (NULL for level 0, whose t is a constant).
+ * Both NULL with stop_level_grad = 1. */
+nof_status nof_mipnerf_cross_view(nof_mipnerf* h, int32_t level, const float** w_grad, const float** t_grad);
 /* sum over rays and levels of lambda_l * m_r |C - p|^2 / sum m (fused path only; synchronises) */
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
@@ -601,6 +616,29 @@ nof_status nof_kernel_render_grad(int32_t n, int32_t samples, const float* densi
                                   const float* dev_g, const float* pixels, const float* loss_mults,
                                   float loss_mult_sum, float lambda, float* density_grad, float* rgb_grad,
                                   void* stream);
+/* The cross-level adjoints (nof_config.stop_level_grad = 0), for parity tests.
+ * nof_kernel_render_grad_ex: nof_kernel_render_grad plus dev_w_grad ([n][S] or NULL: an extra dL/dw_k, folded into
+ * e_k = g.c_k - G + q_k) and dev_t_grad ([n][S + 1] or NULL, overwritten: dL/dt through delta_k = t_{k+1} - t_k).
+ * With both NULL it is nof_kernel_render_grad, bit for bit. */
+nof_status nof_kernel_render_grad_ex(int32_t n, int32_t samples, const float* density, const float* rgb,
+                                     const float* t, const float* dirs, int32_t white_bkgd, const float* comp_rgb,
+                                     const float* dev_g, const float* pixels, const float* loss_mults,
+                                     float loss_mult_sum, float lambda, float* density_grad, float* rgb_grad,
+                                     const float* dev_w_grad, float* dev_t_grad, void* stream);
+/* The adjoint of nof_kernel_sample_pdf (the same sampling arguments; the forward's bin index, clamps, cdf
+ * saturation, pad branch and blur-pool max picks are recomputed and held): dev_t_out_grad [n][S_out + 1] ->
+ * dev_w_grad [n][S_in] and dev_t_in_grad [n][S_in + 1] (or NULL: not wanted), both overwritten. */
+nof_status nof_kernel_sample_pdf_grad(int32_t n, int32_t samples_in, const float* t_in, const float* weights,
+                                      int32_t samples_out, float padding, int32_t randomized, uint64_t seed,
+                                      uint32_t step, uint32_t level, uint32_t ray_base, const float* dev_t_out_grad,
+                                      float* dev_w_grad, float* dev_t_in_grad, void* stream);
+/* The adjoint of cast + IPE with respect to t: dev_enc_pos / dev_enc_pos_grad [n S][6 (max_deg - min_deg)] in the
+ * any-shape encoder's feature order (the stored forward encoding and dL/d of it) -> dev_t_grad [n][S + 1],
+ * overwritten.  S a multiple of 64; 16-byte aligned encodings. */
+nof_status nof_kernel_encode_grad(int32_t n, int32_t samples, const float* t, const float* origins,
+                                  const float* dirs, const float* radii, int32_t ray_shape, int32_t min_deg,
+                                  int32_t max_deg, const float* dev_enc_pos, const float* dev_enc_pos_grad,
+                                  float* dev_t_grad, void* stream);
 nof_status nof_kernel_adam(int64_t n, float* params, const float* grads, float* m, float* v, float lr,
                            int32_t iteration, void* stream);
 

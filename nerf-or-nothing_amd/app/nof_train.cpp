@@ -66,6 +66,7 @@ struct Args {
   // MipNerfModel options (MipNerfModel.cs:14-15,20,22): LinDisp, RayShape, DensityBias, RgbPadding
   bool lindisp = false, cylinder = false;
   float density_bias = -1.0f, rgb_padding = 0.001f;
+  bool no_stop_level_grad = false;  // MipNerfModel.StopLevelGrad = false (MipNerfModel.cs:13)
   // Config (TrainState.cs:54-58)
   float lr_init = 5e-4f, lr_final = 5e-6f, lr_delay_mult = 0.01f;
   int max_steps = 1000000, lr_delay_steps = 2500;
@@ -84,6 +85,7 @@ struct Args {
                "                 [--samples S0,S1[,...]]  (e.g. BASELINE configs[0]: --net-depth 4 --net-width 128 "
                "--samples 64,64)\n"
                "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n"
+               "                 [--no-stop-level-grad]\n"
                "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n");
   std::exit(code);
 }
@@ -116,6 +118,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--cylinder") a.cylinder = true;
     else if (k == "--density-bias") a.density_bias = std::strtof(val(), nullptr);
     else if (k == "--rgb-padding") a.rgb_padding = std::strtof(val(), nullptr);
+    else if (k == "--no-stop-level-grad") a.no_stop_level_grad = true;
     else if (k == "--grad-max-norm") a.grad_max_norm = std::strtof(val(), nullptr);
     else if (k == "--grad-max-val") a.grad_max_val = std::strtof(val(), nullptr);
     else if (k == "--weight-decay") a.weight_decay = std::strtof(val(), nullptr);
@@ -257,6 +260,7 @@ int main(int argc, char** argv) {
     R.cfg.ray_shape = a.cylinder ? NOF_RAY_CYLINDRICAL : NOF_RAY_CONICAL;
     R.cfg.density_bias = a.density_bias;
     R.cfg.rgb_padding = a.rgb_padding;
+    R.cfg.stop_level_grad = a.no_stop_level_grad ? 0 : 1;
     if (a.net_depth) R.cfg.net_depth = a.net_depth;  // other shapes: the any-shape fp32 path
     if (a.net_width) R.cfg.net_width = a.net_width;
     if (a.net_depth_condition) R.cfg.net_depth_condition = a.net_depth_condition;

@@ -101,6 +101,7 @@ void nof_config_default(nof_config* c) {
   c->ray_shape = NOF_RAY_CONICAL;
   c->density_bias = -1.0f;  // MNcs:20
   c->rgb_padding = 0.001f;  // MNcs:22
+  c->stop_level_grad = 1;   // MNcs:13
 }
 
 size_t nof_config_size(void) { return sizeof(nof_config); }
@@ -227,6 +228,9 @@ nof_status nof_mipnerf_get_rng(nof_mipnerf* h, uint64_t* seed, uint32_t* step, u
 }
 nof_status nof_mipnerf_level_view(nof_mipnerf* h, int32_t level, nof_level_view* out) {
   return guard([&] { ARG(h && out); *out = h->impl->level_view(level); });
+}
+nof_status nof_mipnerf_cross_view(nof_mipnerf* h, int32_t level, const float** w_grad, const float** t_grad) {
+  return guard([&] { ARG(h && w_grad && t_grad); h->impl->cross_view(level, w_grad, t_grad); });
 }
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out) {
   return guard([&] { ARG(h && out); DEV(h); *out = h->impl->loss(); });
@@ -715,6 +719,49 @@ nof_status nof_kernel_render_grad(int32_t n, int32_t S, const float* sigma, cons
     ARG(g || (pix && lm && msum > 0.0f));
     NOF_HIP(nof::launch_render_bwd(n, S, sigma, rgb, t, d, white, C, g, pix, lm, msum, lam, dsigma, drgb, nullptr,
                                    (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_render_grad_ex(int32_t n, int32_t S, const float* sigma, const float* rgb, const float* t,
+                                     const float* d, int32_t white, const float* C, const float* g, const float* pix,
+                                     const float* lm, float msum, float lam, float* dsigma, float* drgb,
+                                     const float* w_grad, float* t_grad, void* stream) {
+  if (!w_grad && !t_grad)
+    return nof_kernel_render_grad(n, S, sigma, rgb, t, d, white, C, g, pix, lm, msum, lam, dsigma, drgb, stream);
+  return guard([&] {
+    ARG(n >= 0 && sigma && rgb && t && d && C && dsigma && drgb);
+    ARG(g || (pix && lm && msum > 0.0f));
+    nof::RenderBwdXArgs a{};
+    a.n = n; a.S = S; a.white = white; a.d = d; a.pix = pix; a.lossmult = lm; a.msum = msum;
+    a.sigma = sigma; a.rgb = rgb; a.t = t; a.C = C; a.g_ext = g; a.lam = lam; a.dsigma = dsigma; a.drgb = drgb;
+    a.q = w_grad; a.t_grad = t_grad;
+    NOF_HIP(nof::launch_render_bwd_x(a, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_sample_pdf_grad(int32_t n, int32_t S_in, const float* t_in, const float* w, int32_t S_out,
+                                      float padding, int32_t rnd, uint64_t seed, uint32_t step, uint32_t level,
+                                      uint32_t ray_base, const float* t_out_grad, float* w_grad, float* t_in_grad,
+                                      void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && S_in > 1 && S_in <= 512 && S_out > 0 && S_out <= 512 && t_in && w && t_out_grad && w_grad);
+    nof::SamplePdfGradArgs a{};
+    a.n = n; a.S_in = S_in; a.S_out = S_out; a.t_in = t_in; a.w = w; a.padding = padding; a.randomized = rnd;
+    a.seed = seed; a.step = step; a.level = level; a.ray_base = ray_base;
+    a.t_out_grad = t_out_grad; a.w_grad = w_grad; a.t_in_grad = t_in_grad;
+    NOF_HIP(nof::launch_sample_pdf_grad(a, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_encode_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d,
+                                  const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                                  const float* enc, const float* denc, float* t_grad, void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && S >= 64 && S <= 512 && S % 64 == 0 && t && o && d && radii && enc && denc && t_grad);
+    ARG((ray_shape == NOF_RAY_CONICAL || ray_shape == NOF_RAY_CYLINDRICAL) && min_deg >= 0 && max_deg > min_deg &&
+        max_deg <= 24);
+    nof::EncodeGradArgs a{};
+    a.n = n; a.S = S; a.P = 6 * (max_deg - min_deg); a.min_deg = min_deg;
+    a.cylinder = ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    a.t = t; a.o = o; a.d = d; a.radius = radii; a.enc = enc; a.denc = denc; a.t_grad = t_grad;
+    NOF_HIP(nof::launch_encode_grad(a, (hipStream_t)stream));
   });
 }
 nof_status nof_kernel_adam(int64_t n, float* p, const float* g, float* m, float* v, float lr, int32_t it,

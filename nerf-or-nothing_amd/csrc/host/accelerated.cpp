@@ -123,6 +123,12 @@ static void check_cfg(const nof_config& c) {
   NOF_REQUIRE(std::isfinite(c.density_bias) && std::isfinite(c.rgb_padding) && c.rgb_padding >= 0.0f &&
                   c.rgb_padding < 0.5f,
               "density_bias must be finite, rgb_padding in [0, 0.5)");
+  NOF_REQUIRE(c.stop_level_grad == 0 || c.stop_level_grad == 1, "stop_level_grad must be 0 or 1");
+  if (c.stop_level_grad == 0 && c.precision != NOF_PRECISION_F32 && c.precision != NOF_PRECISION_F16_PRODUCTS)
+    throw Error(NOF_ERR_UNSUPPORTED,
+                "stop_level_grad = 0 needs the gradient with respect to the MLP's encoded input, which the fused "
+                "8x256 kernels do not produce: use NOF_PRECISION_F32 or NOF_PRECISION_F16_PRODUCTS (the any-shape "
+                "path, every network)");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -159,7 +165,8 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
   // (F16_PRODUCTS is the any-shape path's mode: the reference network runs there too)
   generic_ = !(D == 8 && W == 256 && Dc == 1 && Wc == 128 && cfg.skip_layer == 4 && cfg.min_deg_point == 0 &&
                cfg.max_deg_point == 16 && cfg.deg_view == 4) ||
-             cfg.precision == NOF_PRECISION_F16_PRODUCTS;
+             cfg.precision == NOF_PRECISION_F16_PRODUCTS || cfg.stop_level_grad == 0;
+  cross_ = cfg.stop_level_grad == 0 && cfg.num_levels > 1;  // (one level: nothing crosses)
 
   params_.alloc(P_);
   grads_.alloc(P_);
@@ -851,6 +858,15 @@ void AcceleratedMLP::gen_alloc() {
   gd1_.alloc((size_t)max_M_ * Wm);
   gdz_.alloc((size_t)max_M_ * 4);
   gray_.alloc((size_t)cfg_.max_rays * gWc_);
+  if (cross_) {  // levels >= 1 only
+    size_t Mx = 0;
+    for (int l = 1; l < NL; ++l) Mx = std::max(Mx, (size_t)lv_[l].cap);
+    int contrib = 1;  // layer 0 and the skip layers
+    for (int l = 1; l < gD_; ++l) contrib += l % gskip_ == 0 ? 1 : 0;
+    gd2_.alloc(Mx * gW_);
+    gdenc_.alloc(Mx * gP_);
+    if (contrib > 2) gdenc_part_.alloc((size_t)((contrib + 1) / 2) * Mx * gP_);
+  }
   if (f16_products()) {
     amax_.alloc(NL);
     NOF_HIP(hipMemset(amax_.p, 0, NL * sizeof(uint32_t)));
@@ -984,7 +1000,18 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
   te(kTMlpFwd);
 }
 
-void AcceleratedMLP::gen_backward(int level, const float* color_grad, const float* density_grad, int acc) {
+void AcceleratedMLP::gradient_level_cross(int level, const float* color_grad, const float* density_grad,
+                                          int accumulate, const float** denc) {
+  NOF_REQUIRE(generic_ && cross_, "gradient_level_cross needs stop_level_grad = 0");
+  NOF_REQUIRE(level >= 0 && level < (int)lv_.size() && lv_[level].M > 0, "get_gradient before get_output for this level");
+  NOF_REQUIRE(color_grad && density_grad, "null output gradients");
+  NOF_REQUIRE(!denc || level > 0, "level 0's encoding is a constant");
+  gen_backward(level, color_grad, density_grad, accumulate, denc != nullptr);
+  if (denc) *denc = gdenc_.p;
+}
+
+void AcceleratedMLP::gen_backward(int level, const float* color_grad, const float* density_grad, int acc,
+                                  bool want_denc) {
   Level& L = lv_[level];
   GenLevel& G = gl_[level];
   const bool dry = wg_need_ != nullptr;  // slab sizing (gen_alloc): only gen_wgrad's records, no launches
@@ -1072,6 +1099,29 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     masked(a, D - 1, H(D - 1), W);
     std::swap(cur, nxt);
   }
+  // stop_level_grad = 0: dEnc = delta_0 W_0 + sum over skip layers s of delta_s W_s[:, W : W + P], two layers per
+  // product (the second k source), in descending layer order.  A skip layer's delta waits in `pend` for its
+  // partner: its buffer leaves the ping-pong and `spare` takes its place.  More than one product: each into its
+  // own part, then one ordered sum.
+  float *pend = nullptr, *spare = gd2_.p;
+  int pend_l = -1, nparts = 0;
+  const bool parts = want_denc && gdenc_part_.p != nullptr;
+  auto denc_product = [&](const float* dA, int la, const float* dB, int lb) {
+    nof::GemmArgs a;
+    a.M = M; a.N = P; a.K1 = W;
+    a.A1 = gsrc(dA, W, 1);
+    a.B1 = gsrc(prm + woff_[la] + (la > 0 ? W : 0), 1, in_[la]);
+    if (dB) {
+      a.K2 = W;
+      a.A2 = gsrc(dB, W, 1);
+      a.B2 = gsrc(prm + woff_[lb] + (lb > 0 ? W : 0), 1, in_[lb]);
+    }
+    a.C = parts ? gdenc_part_.p + (size_t)nparts * M * P : gdenc_.p;
+    a.ci = P; a.cj = 1;
+    if (sc) { a.scale_amax = sc; a.scale_src = 1; }
+    gemm1(a);
+    ++nparts;
+  };
   for (int l = D - 1; l >= 0; --l) {  // trunk
     float* gw = gr + woff_[l];
     if (l > 0) {
@@ -1080,11 +1130,34 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     } else {
       gen_wgrad(gw, P, cur, W, W, gsrc(G.ep, 1, P), P, M, acc, gr + boff_[l], sc);
     }
+    const bool contributes = want_denc && !dry && (l == 0 || l % gskip_ == 0);
+    bool retire = false;  // cur becomes pend
+    if (contributes) {
+      if (pend) {
+        denc_product(pend, pend_l, cur, l);
+        spare = pend;
+        pend = nullptr;
+      } else if (l == 0) {
+        denc_product(cur, 0, nullptr, -1);
+      } else {
+        retire = true;
+      }
+    }
     if (l > 0) {
       dx(cur, W, W, l, l - 1, H(l - 1), W, nxt);
       std::swap(cur, nxt);
+      if (retire) {  // (nxt is the buffer delta_l lives in)
+        pend = nxt;
+        pend_l = l;
+        nxt = spare;
+        spare = nullptr;
+      }
     }
   }
+  if (nparts > 1)
+    NOF_HIP(nof::launch_slab_sum(M, P, P, nparts, gdenc_part_.p, (int64_t)M * P, gdenc_.p, P, 0, st_));
+  else if (nparts == 1 && parts)
+    NOF_HIP(hipMemcpyAsync(gdenc_.p, gdenc_part_.p, (size_t)M * P * sizeof(float), hipMemcpyDeviceToDevice, st_));
   if (!dry) {
     int batches;
     NOF_HIP(nof::launch_slab_sums(wg_jobs_.data(), (int)wg_jobs_.size(), st_, &batches));
@@ -1125,6 +1198,16 @@ AcceleratedMipNeRF::AcceleratedMipNeRF(const nof_config& cfg) : mlp(nullptr), cf
     t_[l].alloc(N * (S + 1)); w_[l].alloc(N * S); C_[l].alloc(3 * N); acc_[l].alloc(N); dist_[l].alloc(N);
     dsig_[l].alloc(N * S); drgb_[l].alloc(3 * N * S); loss_rays_[l].alloc(N);
   }
+  cross_ = mlp->cross();
+  if (cross_) {
+    q_.resize(L); dtr_.resize(L); dtb_.resize(L); dt_.resize(L);
+    for (int l = 0; l < L; ++l) {
+      const size_t S = cfg.num_samples[l];
+      if (l + 1 < L) q_[l].alloc(N * S);
+      if (l >= 1) { dtr_[l].alloc(N * (S + 1)); dt_[l].alloc(N * (S + 1)); }
+      if (l >= 1 && l + 1 < L) dtb_[l].alloc(N * (S + 1));
+    }
+  }
 }
 
 AcceleratedMipNeRF::~AcceleratedMipNeRF() {
@@ -1164,7 +1247,7 @@ float* const* AcceleratedMipNeRF::GetGradientDevice(int n, const float* o, const
 
 float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, const float* radii, const float* nears,
                                       const float* fars, const float* lm, const float* pix, float msum,
-                                      nof_output_grad_fn cb, void* user, uint32_t flags) {
+                                      nof_output_grad_fn cb_in, void* user, uint32_t flags) {
   static const char* const kFwd[] = {"nof:level0_forward", "nof:level1_forward", "nof:level2_forward",
                                      "nof:level3_forward"};
   static const char* const kBwd[] = {"nof:backward"};
@@ -1184,6 +1267,8 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
       timer.end(kTSample);
     }
     mlp->forward_fused(lv, n, S, t_[lv].p, o, d, radii);
+    // (stop_level_grad = 0 walks the levels one by one, as a callback does: the same forward launches)
+    const bool cb = cb_in || cross_;
     if (lv + 1 < L || cb) timer.begin(kTRenderFwd);  // (a timer pair only around a launch)
     if (lv + 1 < L) {  // this level's integrator and the next level's resampler (ResampleAlongRay) in one launch
       nof::RenderPdfArgs ra{};
@@ -1198,6 +1283,14 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     }
     if (lv + 1 < L || cb) timer.end(kTRenderFwd);
   }
+  if (cross_) {
+    float* const* g = run_cross(n, o, d, radii, lm, pix, msum, cb_in, user, flags);
+    last_n_ = n;
+    last_fused_ = cb_in == nullptr;
+    ++step_;
+    return g;
+  }
+  nof_output_grad_fn cb = cb_in;
   // MNcpp:125-134: the loss gradient and the integrator adjoint of every level (with the f16 modes' delta
   // maxima), levels of equal sample count in one launch when no callback supplies dL/dC, else one level
   // at a time after its callback
@@ -1247,6 +1340,63 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
   last_fused_ = cb == nullptr;
   ++step_;
   return grads;
+}
+
+// stop_level_grad = 0: the backward of a step whose forward has run, levels descending.  Level l:
+// the integrator adjoint with q^l (from level l + 1's resampler) -> dsigma, drgb and dt_render; the MLP backward
+// (+ dEnc for l >= 1); the encoding adjoint, which also forms dt^l = (dt_render + dt_enc) + dt_bins; the
+// resampler adjoint dt^l -> q^{l-1} and, for l - 1 >= 1, dt_bins^{l-1}.
+float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* d, const float* radii,
+                                            const float* lm, const float* pix, float msum, nof_output_grad_fn cb,
+                                            void* user, uint32_t flags) {
+  const int L = cfg_.num_levels;
+  std::vector<const float*> g(L, nullptr);
+  if (cb)  // every callback first, in order 0..L-1 (MNcpp:125-127)
+    for (int lv = 0; lv < L; ++lv) {
+      g[lv] = reinterpret_cast<const float*>(cb(user, (uint64_t)(uintptr_t)C_[lv].p, lv, msum, (uint64_t)(uintptr_t)lm));
+      NOF_REQUIRE(g[lv] != nullptr, "output-gradient callback returned null");
+    }
+  TraceRange br("nof:backward");
+  for (int lv = L - 1; lv >= 0; --lv) {
+    const int S = cfg_.num_samples[lv];
+    nof::RenderBwdXArgs ra{};
+    ra.n = n; ra.S = S; ra.white = cfg_.white_bkgd; ra.d = d; ra.pix = pix; ra.lossmult = lm; ra.msum = msum;
+    ra.nonfinite = mlp->numeric_flags();
+    ra.sigma = mlp->density(lv); ra.rgb = mlp->rgb(lv); ra.t = t_[lv].p; ra.C = C_[lv].p; ra.g_ext = g[lv];
+    ra.lam = lv < L - 1 ? cfg_.coarse_loss_mult : 1.0f;
+    ra.dsigma = dsig_[lv].p; ra.drgb = drgb_[lv].p; ra.loss_rays = cb ? nullptr : loss_rays_[lv].p;
+    ra.q = lv + 1 < L ? q_[lv].p : nullptr;
+    ra.t_grad = lv >= 1 ? dtr_[lv].p : nullptr;
+    timer.begin(kTRenderBwd);
+    NOF_HIP(nof::launch_render_bwd_x(ra, st_));
+    timer.end(kTRenderBwd);
+    const float* denc = nullptr;
+    mlp->gradient_level_cross(lv, drgb_[lv].p, dsig_[lv].p, (lv < L - 1 || (flags & NOF_GRAD_ACCUMULATE)) ? 1 : 0,
+                              lv >= 1 ? &denc : nullptr);
+    if (lv == 0) break;
+    timer.begin(kTSample);
+    nof::EncodeGradArgs ea{};
+    ea.n = n; ea.S = S; ea.P = 6 * (cfg_.max_deg_point - cfg_.min_deg_point); ea.min_deg = cfg_.min_deg_point;
+    ea.cylinder = cfg_.ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    ea.t = t_[lv].p; ea.o = o; ea.d = d; ea.radius = radii; ea.enc = mlp->enc_pos(lv); ea.denc = denc;
+    ea.add0 = dtr_[lv].p; ea.add1 = lv + 1 < L ? dtb_[lv].p : nullptr;
+    ea.t_grad = dt_[lv].p;
+    NOF_HIP(nof::launch_encode_grad(ea, st_));
+    nof::SamplePdfGradArgs sa{};
+    sa.n = n; sa.S_in = cfg_.num_samples[lv - 1]; sa.S_out = S; sa.t_in = t_[lv - 1].p; sa.w = w_[lv - 1].p;
+    sa.padding = cfg_.resample_padding; sa.randomized = cfg_.randomized; sa.seed = seed_; sa.step = step_;
+    sa.level = (uint32_t)lv; sa.ray_base = ray_base_;
+    sa.t_out_grad = dt_[lv].p; sa.w_grad = q_[lv - 1].p; sa.t_in_grad = lv - 1 >= 1 ? dtb_[lv - 1].p : nullptr;
+    NOF_HIP(nof::launch_sample_pdf_grad(sa, st_));
+    timer.end(kTSample);
+  }
+  return mlp->publish_cross(flags);
+}
+
+void AcceleratedMipNeRF::cross_view(int level, const float** w_grad, const float** t_grad) const {
+  NOF_REQUIRE(level >= 0 && level < cfg_.num_levels, "level out of range");
+  *w_grad = cross_ ? q_[level].p : nullptr;
+  *t_grad = cross_ ? dt_[level].p : nullptr;
 }
 
 void AcceleratedMipNeRF::Render(int n, const float* o, const float* d, const float* radii, const float* nears,

@@ -164,6 +164,14 @@ class AcceleratedMLP {
   // it writes: the level's amax word to fill (zeroed by this step's pack launch), or null when the mode
   // has none or the word is not fresh; the level's backward then skips its k_delta_amax pass.
   uint32_t* claim_delta_amax(int level);
+  // nof_config.stop_level_grad = 0 (any-shape path only): one level's backward, the caller walking the levels in
+  // descending order; denc != null: also dL/d(the level's encoded input) [M][P] (borrowed until the next call)
+  // = delta_0 W_0 + sum over skip layers s of delta_s W_s[:, W : W + P]
+  bool cross() const { return cross_; }
+  void gradient_level_cross(int level, const float* color_grad, const float* density_grad, int accumulate,
+                            const float** denc);
+  float* const* publish_cross(uint32_t flags) { return gen_publish((flags & NOF_GRAD_PUBLISH) && hook_); }
+  const float* enc_pos(int level) const { return gl_[level].ep; }  // the encoding the level's last forward read
 
  private:
   struct Schedule {
@@ -241,7 +249,12 @@ class AcceleratedMLP {
   DevBuf<float> gray_;                    // per-ray sums of the view layer's dZ [rays][Wc]
   void gen_alloc();
   void gen_forward(int level, const float* enc_pos, const float* enc_dir);
-  void gen_backward(int level, const float* color_grad, const float* density_grad, int accumulate);
+  void gen_backward(int level, const float* color_grad, const float* density_grad, int accumulate,
+                    bool want_denc = false);
+  // stop_level_grad = 0 (allocated only then): a third dZ buffer (a skip layer's delta outlives the ping-pong until
+  // its pair is formed), dL/dEnc [M][P] and, with more than two contributing layers, the pairs' partial sums
+  bool cross_ = false;
+  DevBuf<float> gd2_, gdenc_, gdenc_part_;
   // non-null: gen_backward launches nothing and gen_wgrad records its split-K slab need here instead (the
   // slab is sized at construction by a dry run of the same call sequence a step makes)
   size_t* wg_need_ = nullptr;
@@ -296,6 +309,7 @@ class AcceleratedMipNeRF {
   void set_rng(uint64_t seed, uint32_t step, uint32_t ray_base) { seed_ = seed; step_ = step; ray_base_ = ray_base; }
   void get_rng(uint64_t* seed, uint32_t* step, uint32_t* ray_base) const { *seed = seed_; *step = step_; *ray_base = ray_base_; }
   nof_level_view level_view(int level) const;
+  void cross_view(int level, const float** w_grad, const float** t_grad) const;
   float loss();
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
@@ -324,6 +338,12 @@ class AcceleratedMipNeRF {
   bool last_fused_ = false;
   DevBuf<float> o_, d_, radii_, nears_, fars_, lm_, pix_;
   std::vector<DevBuf<float>> t_, w_, C_, dsig_, drgb_, loss_rays_, acc_, dist_;
+  // stop_level_grad = 0 (allocated only then): q^l = dL/dw^l [n][S] (levels < L - 1); for levels >= 1 the
+  // integrator's and the bin edges' dL/dt^l and their sum with the encoding's [n][S + 1]
+  bool cross_ = false;
+  std::vector<DevBuf<float>> q_, dtr_, dtb_, dt_;
+  float* const* run_cross(int n, const float* o, const float* d, const float* radii, const float* lm, const float* pix,
+                          float msum, nof_output_grad_fn cb, void* user, uint32_t flags);
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -84,6 +84,51 @@ hipError_t launch_render_bwd(const RenderBwdArgs& a, int nlev, hipStream_t st);
 hipError_t launch_output_gradient(int n, const float* C, const float* pix, const float* lossmult,
                                   float loss_mult_sum, float lam, float* g, hipStream_t st);
 
+// One level's loss gradient + adjoint with the cross-level terms (nof_config.stop_level_grad = 0): q (optional,
+// [n][S]) = dL/dw_k from the next level's resampler, folded into e_k = g.c_k - G + q_k; t_grad (optional,
+// [n][S + 1], overwritten) = dL/dt through delta_k = t_{k+1} - t_k: dt_k = ddelta_{k-1} - ddelta_k with
+// ddelta_k = X_k sigma_k |d|.  Otherwise launch_render_bwd's single-level form (its own kernel: the
+// instantiations above are untouched); fwd: the level's integrator forward first, as RenderBwdArgs::fwd_last.
+struct RenderBwdXArgs {
+  int n, S, white;
+  const float *d, *pix, *lossmult;
+  float msum;
+  uint32_t* nonfinite;
+  const float *sigma, *rgb, *t, *C, *g_ext;
+  float lam;
+  float *dsigma, *drgb, *loss_rays;
+  const float* q;
+  float* t_grad;
+  int fwd;
+  float *fwd_C, *fwd_w;
+};
+hipError_t launch_render_bwd_x(const RenderBwdXArgs& a, hipStream_t st);
+
+// ---- crosslevel.hip: the adjoints of cast + IPE and of the resampler (stop_level_grad = 0) ------------
+// t_grad [n][S + 1] (overwritten) = (add0 +) d/dt of sum_{m, F} denc[m][F] enc[m][F](t) (+ add1): enc / denc
+// [n S][P], P = 6 degrees from min_deg in the any-shape encoder's feature order, enc the stored forward
+// encoding; add0 / add1 (optional, [n][S + 1]) are added before / after in that order.  S a multiple of 64.
+struct EncodeGradArgs {
+  int n, S, P, min_deg, cylinder;
+  const float *t, *o, *d, *radius, *enc, *denc;
+  const float *add0, *add1;
+  float* t_grad;
+};
+hipError_t launch_encode_grad(const EncodeGradArgs& a, hipStream_t st);
+// The adjoint of launch_sample_pdf (same sampling arguments): t_out_grad [n][S_out + 1] -> w_grad [n][S_in]
+// and, optional, t_in_grad [n][S_in + 1] (the input t row as the bin edges)
+struct SamplePdfGradArgs {
+  int n, S_in, S_out;
+  const float *t_in, *w;
+  float padding;
+  int randomized;
+  uint64_t seed;
+  uint32_t step, level, ray_base;
+  const float* t_out_grad;
+  float *w_grad, *t_in_grad;
+};
+hipError_t launch_sample_pdf_grad(const SamplePdfGradArgs& a, hipStream_t st);
+
 // ---- mlp_fwd.hip / mlp_bwd.hip -----------------------------------------------------------------
 struct FwdArgs {
   int M, S, encoded;

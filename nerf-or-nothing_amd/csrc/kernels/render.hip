@@ -284,6 +284,85 @@ __global__ __launch_bounds__(256) void k_render_bwd(RenderBwdArgs a) {
   }
 }
 
+// k_render_bwd for one level with the cross-level terms (launch.h RenderBwdXArgs): q_k joins e_k, and the
+// adjoint of delta_k = t_{k+1} - t_k gives dL/dt.  Without q and t_grad its values are k_render_bwd's.
+template <int PER>
+__global__ __launch_bounds__(256) void k_render_bwd_x(RenderBwdXArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= a.n) return;  // wave-uniform; no block barriers below
+  RayState<PER> rs;
+  float Cv[3];
+  if (a.fwd) {
+    render_fwd_ray<PER>(r, lane, a.S, a.sigma, a.rgb, a.t, a.d, a.white, a.fwd_C, a.fwd_w, nullptr, nullptr, a.nonfinite,
+                        nullptr, nullptr, rs, Cv);
+  } else {
+    ray_alpha_T<PER>(a.S, r, lane, a.sigma, a.t, a.d, rs);
+  }
+  float g0, g1, g2;
+  if (a.g_ext) {
+    g0 = a.g_ext[3 * r]; g1 = a.g_ext[3 * r + 1]; g2 = a.g_ext[3 * r + 2];
+  } else {  // AF:356-358 order: 2*m/sum*(C-p)*lambda
+    const float m = a.lossmult[r];
+    const float s = 2.0f * m / a.msum;
+    const float C0 = a.fwd ? Cv[0] : a.C[3 * r], C1 = a.fwd ? Cv[1] : a.C[3 * r + 1], C2 = a.fwd ? Cv[2] : a.C[3 * r + 2];
+    const float e0 = C0 - a.pix[3 * r], e1 = C1 - a.pix[3 * r + 1], e2 = C2 - a.pix[3 * r + 2];
+    g0 = s * e0 * a.lam; g1 = s * e1 * a.lam; g2 = s * e2 * a.lam;
+    if (a.loss_rays && lane == 0) a.loss_rays[r] = a.lam * m * ((e0 * e0 + e1 * e1) + e2 * e2) / a.msum;
+  }
+  const float G = a.white ? (g0 + g1 + g2) : 0.0f;
+  const int k0 = lane * PER;
+  float cr[3 * PER], dc[3 * PER], ds[PER], sg[PER], qk[PER];
+  vload<3 * PER, kRgbAlign<PER>>(a.rgb + ((size_t)r * a.S + k0) * 3, cr);
+  vload<PER, PER>(a.sigma + (size_t)r * a.S + k0, sg);
+  if (a.q) {
+    vload<PER, PER>(a.q + (size_t)r * a.S + k0, qk);
+  } else {
+#pragma unroll
+    for (int p = 0; p < PER; ++p) qk[p] = 0.0f;
+  }
+  float wk[PER], ek[PER];
+  float ls = 0.0f;
+#pragma unroll
+  for (int p = 0; p < PER; ++p) {
+    wk[p] = rs.a[p] * rs.T[p];
+    ek[p] = (g0 * cr[3 * p] + g1 * cr[3 * p + 1]) + g2 * cr[3 * p + 2] - G;
+    if (a.q) ek[p] += qk[p];
+    dc[3 * p] = g0 * wk[p]; dc[3 * p + 1] = g1 * wk[p]; dc[3 * p + 2] = g2 * wk[p];
+    ls += wk[p] * ek[p];
+  }
+  vstore<3 * PER, kRgbAlign<PER>>(a.drgb + ((size_t)r * a.S + k0) * 3, dc);
+  float inc = ls;  // inclusive suffix sum over lanes
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_down(inc, o, 64);
+    if (lane + o < 64) inc += y;
+  }
+  float after = __shfl_down(inc, 1, 64);  // sum over lanes > lane
+  if (lane == 63) after = 0.0f;
+  float dd[PER];  // dL/ddelta_k = X_k sigma_k |d|
+#pragma unroll
+  for (int p = PER - 1; p >= 0; --p) {
+    const float Tn = rs.T[p] * (1.0f - rs.a[p]);
+    const float X = Tn * ek[p] - after;
+    ds[p] = X * (rs.tv[p + 1] - rs.tv[p]) * rs.dl;
+    dd[p] = X * sg[p] * rs.dl;
+    after += wk[p] * ek[p];
+  }
+  vstore<PER, PER>(a.dsigma + (size_t)r * a.S + k0, ds);
+  if (a.t_grad) {  // dt_k = ddelta_{k-1} - ddelta_k (ddelta_{-1} = ddelta_S = 0)
+    float prev = __shfl_up(dd[PER - 1], 1, 64);
+    if (lane == 0) prev = 0.0f;
+    float* tg = a.t_grad + (size_t)r * (a.S + 1) + k0;
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+      tg[p] = prev - dd[p];
+      prev = dd[p];
+    }
+    if (lane == 63) tg[PER] = prev;
+  }
+}
+
 __global__ void k_output_gradient(int n, const float* __restrict__ C, const float* __restrict__ pix,
                                   const float* __restrict__ lossmult, float msum, float lam, float* __restrict__ g) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -339,6 +418,15 @@ hipError_t launch_render_bwd(int n, int S, const float* sigma, const float* rgb,
   L.sigma = sigma; L.rgb = rgb; L.t = t; L.C = C; L.g_ext = g_ext; L.lam = lam;
   L.dsigma = dsigma; L.drgb = drgb; L.loss_rays = loss_rays;
   return launch_render_bwd(a, 1, st);
+}
+
+hipError_t launch_render_bwd_x(const RenderBwdXArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.fwd && (a.g_ext || !a.fwd_C || !a.fwd_w)) return hipErrorInvalidValue;
+  const dim3 grid((a.n + 3) / 4), block(256);
+  const int S = a.S;
+  NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL(k_render_bwd_x<PER>, grid, block, 0, st, a));
+  return hipGetLastError();
 }
 
 hipError_t launch_output_gradient(int n, const float* C, const float* pix, const float* lossmult,

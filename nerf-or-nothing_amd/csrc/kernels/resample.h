@@ -57,14 +57,15 @@ __device__ __forceinline__ void cdf_chain(const float* __restrict__ pdf, float* 
 // LDS of one ray (3 B + 2 floats): wb[B] (blurred weights, then pdf), cdf[B + 1] (holding the input weights
 // on entry), trs[B + 1] (the ray's input t row).  Entry: cdf[0, B) and trs[0, B] staged and published by a
 // barrier; s_wsum: a workgroup-shared float.  One 64-lane workgroup per ray.
-__device__ __forceinline__ void resample_staged(int r, int lane, int B, float* smem, float* s_wsum, int S_out,
-                                                float padding, int randomized, uint64_t seed, uint32_t step,
-                                                uint32_t level, uint32_t ray_base, float* __restrict__ t_out,
-                                                int32_t* __restrict__ idx_out) {
+// resample_staged = resample_cdf, then per output sample resample_u and resample_bin; the resampler's adjoint
+// (crosslevel.hip) recomputes the forward's decisions with the same three.
+// resample_cdf: wb <- pdf, cdf row <- cdf, *s_wsum <- the normalising sum; s_pad (optional, workgroup-shared): the
+// pad the empty-weights branch added (0: not taken).  Ends with a barrier.
+__device__ __forceinline__ void resample_cdf(int lane, int B, float* smem, float* s_wsum, float padding,
+                                             float* s_pad = nullptr) {
 #pragma clang fp contract(off)
   float* wb = smem;
   float* cdf = smem + B;
-  const float* trs = smem + 2 * B + 1;
   // blur-pool: wmax[i] = max(pad[i], pad[i+1]); wb[i] = .5(wmax[i] + wmax[i+1]) + padding (MH:646-661)
   for (int i = lane; i < B; i += 64) {
     const float w0 = cdf[i];
@@ -86,6 +87,7 @@ __device__ __forceinline__ void resample_staged(int r, int lane, int B, float* s
       wsum = wsum + pad;
     }
     *s_wsum = wsum;
+    if (s_pad) *s_pad = pad;
   }
   __syncthreads();
   const float wsum = *s_wsum;
@@ -93,21 +95,42 @@ __device__ __forceinline__ void resample_staged(int r, int lane, int B, float* s
   __syncthreads();
   if (lane == 0) cdf_chain(wb, cdf, B);  // sequential fp32 cumsum: a parallel scan would change the rounding
   __syncthreads();
+}
+
+// sample s's cdf coordinate u (ns = S_out + 1 samples, s1 = 1 / ns)
+__device__ __forceinline__ float resample_u(int r, int s, int ns, float s1, int randomized, uint64_t seed, uint32_t step,
+                                            uint32_t level, uint32_t ray_base) {
+#pragma clang fp contract(off)
+  if (randomized) {
+    const float rr = philox_uniform(seed, step, level, kStreamPdf, ray_base + (uint32_t)r, (uint32_t)s);
+    return fminf((float)s * s1 + rr * (s1 - 1e-7f), 1.0f - 1e-7f);
+  }
+  return (float)s * ((1.0f - 1e-7f) / (float)(ns - 1));
+}
+
+// largest i in [0, B-1] with cdf[i] <= u (cdf[0] = 0 <= u)
+__device__ __forceinline__ int resample_bin(const float* cdf, int B, float u) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cdf[mid] <= u) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void resample_staged(int r, int lane, int B, float* smem, float* s_wsum, int S_out,
+                                                float padding, int randomized, uint64_t seed, uint32_t step,
+                                                uint32_t level, uint32_t ray_base, float* __restrict__ t_out,
+                                                int32_t* __restrict__ idx_out) {
+#pragma clang fp contract(off)
+  resample_cdf(lane, B, smem, s_wsum, padding);
+  const float* cdf = smem + B;
+  const float* trs = smem + 2 * B + 1;
   const int ns = S_out + 1;
   const float s1 = 1.0f / (float)ns;
   for (int s = lane; s < ns; s += 64) {
-    float u;
-    if (randomized) {
-      const float rr = philox_uniform(seed, step, level, kStreamPdf, ray_base + (uint32_t)r, (uint32_t)s);
-      u = fminf((float)s * s1 + rr * (s1 - 1e-7f), 1.0f - 1e-7f);
-    } else {
-      u = (float)s * ((1.0f - 1e-7f) / (float)(ns - 1));
-    }
-    int lo = 0, hi = B - 1;  // largest i in [0, B-1] with cdf[i] <= u (cdf[0] = 0 <= u)
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (cdf[mid] <= u) lo = mid; else hi = mid - 1;
-    }
+    const float u = resample_u(r, s, ns, s1, randomized, seed, step, level, ray_base);
+    const int lo = resample_bin(cdf, B, u);
     NOF_DCHECK(lo >= 0 && lo < B, kChkSampleIdx);  // a bin of the input t row
     const float b0 = trs[lo], b1 = trs[lo + 1], c0 = cdf[lo], c1 = cdf[lo + 1];
     const float denom = c1 - c0;

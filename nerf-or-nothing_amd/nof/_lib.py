@@ -44,6 +44,7 @@ class nof_config(C.Structure):
         ("seed", C.c_uint64), ("stream", C.c_void_p), ("precision", C.c_int32), ("grad_buckets", C.c_int32),
         ("lindisp", C.c_int32), ("ray_shape", C.c_int32),
         ("density_bias", C.c_float), ("rgb_padding", C.c_float),
+        ("stop_level_grad", C.c_int32),
     ]
 
 
@@ -128,6 +129,7 @@ SIGNATURES = {
     "nof_mipnerf_set_rng": [P, U64, U32, U32],
     "nof_mipnerf_get_rng": [P, C.POINTER(U64), C.POINTER(U32), C.POINTER(U32)],
     "nof_mipnerf_level_view": [P, I32, C.POINTER(nof_level_view)],
+    "nof_mipnerf_cross_view": [P, I32, C.POINTER(P), C.POINTER(P)],
     "nof_mipnerf_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],
@@ -213,6 +215,9 @@ SIGNATURES = {
     "nof_kernel_encode": [I32, I32, P, P, P, P, P, P],
     "nof_kernel_render": [I32, I32, P, P, P, P, I32, P, P, P],
     "nof_kernel_render_grad": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P],
+    "nof_kernel_render_grad_ex": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P],
+    "nof_kernel_sample_pdf_grad": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P, P],
+    "nof_kernel_encode_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P],
     "nof_kernel_adam": [C.c_int64, P, P, P, P, F, I32, P],
     "nof_kernel_gemm_h": [C.POINTER(nof_gemm_args), P],
 }

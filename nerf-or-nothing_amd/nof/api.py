@@ -332,6 +332,17 @@ class AcceleratedMipNeRF:
     def level_numpy(self, level: int) -> dict:
         return {k: to_numpy(p, shp) for k, (p, shp) in self.level_view(level).items()}
 
+    def cross_numpy(self, level: int) -> dict:
+        """stop_level_grad = 0: the last step's cross-level terms of `level` (include/nof.h
+        nof_mipnerf_cross_view): "w_grad" [n, S] = dL/dw from the next level's resampler, "t_grad" [n, S + 1] =
+        dL/dt; None where the level has none (the last level / level 0, or stop_level_grad = 1)."""
+        v = L.nof_level_view()
+        call("nof_mipnerf_level_view", self._h, level, C.byref(v))
+        q, dt = C.c_void_p(), C.c_void_p()
+        call("nof_mipnerf_cross_view", self._h, level, C.byref(q), C.byref(dt))
+        return {"w_grad": to_numpy(q.value, (v.n, v.samples)) if q.value else None,
+                "t_grad": to_numpy(dt.value, (v.n, v.samples + 1)) if dt.value else None}
+
     def loss(self) -> float:
         out = C.c_float()
         call("nof_mipnerf_loss", self._h, C.byref(out))

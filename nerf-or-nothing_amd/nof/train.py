@@ -247,6 +247,8 @@ def parse_args(argv=None):
     ap.add_argument("--cylinder", action="store_true")
     ap.add_argument("--density-bias", type=float, default=-1.0)
     ap.add_argument("--rgb-padding", type=float, default=0.001)
+    ap.add_argument("--no-stop-level-grad", action="store_true",
+                    help="MipNerfModel.StopLevelGrad = false: backprop across levels (f32 / f16p, the any-shape path)")
     # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70; 0 = off) and the step statistics
     ap.add_argument("--grad-max-norm", type=float, default=0.0, help="clip the gradient's global norm")
     ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
@@ -280,7 +282,7 @@ def main(argv=None):
     if a.samples:
         net["num_samples"] = tuple(a.samples)
     net.update(lindisp=int(a.lindisp), ray_shape=int(a.cylinder), density_bias=a.density_bias,
-               rgb_padding=a.rgb_padding)
+               rgb_padding=a.rgb_padding, stop_level_grad=0 if a.no_stop_level_grad else 1)
     if a.scene:
         ds = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device, holdout=a.holdout)
     elif a.records:
