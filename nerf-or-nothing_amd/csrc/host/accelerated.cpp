@@ -808,17 +808,37 @@ static nof::GemmSrc gsrc(const float* p, int64_t si, int64_t sk, int idiv = 1) {
   return s;
 }
 
-void AcceleratedMLP::gemm1(nof::GemmArgs a) {  // no split: one k chunk
-  a.kchunk = (a.K1 + a.K2 + 15) / 16 * 16;
-  a.slab_stride = 0;
+// Every GEMM of the any-shape path picks its kernel here.  ksplit == 1: one k chunk.  ws: the weight-stationary
+// kernel (gemm_ws.hip) may take the product where the mode is fp32 and the shape fits it; a masked product
+// (a.G) is given the layer's ReLU bits in a.mask_in where the forward wrote them, and takes that kernel with the
+// bits or k_gemm / k_gemm_h with G.  f32: fp32 k_gemm in every mode.  Returns whether the weight-stationary
+// kernel ran.
+bool AcceleratedMLP::gen_product(nof::GemmArgs a, int ksplit, bool ws, bool f32) {
   int v;
-  if (f16_products()) {
-    NOF_HIP(nof::launch_gemm_h(a, 1, st_, &v));
-    tally_h(v);
-    return;
+  if (ksplit == 1) {
+    a.kchunk = (a.K1 + a.K2 + 15) / 16 * 16;
+    a.slab_stride = 0;
   }
-  NOF_HIP(nof::launch_gemm(a, 1, st_, &v));
-  tally(v);
+  if (ws && !f16_products() && (!a.G || a.mask_in)) {
+    nof::GemmArgs w = a;
+    w.G = nullptr;
+    if (nof::gemm_ws_fits(w)) {
+      NOF_HIP(nof::launch_gemm_ws(w, st_, &v));
+      tally(v);
+      return true;
+    }
+  }
+  NOF_REQUIRE(a.G || !a.mask_in, "a ReLU-bit mask needs the weight-stationary kernel");
+  a.mask_in = nullptr;
+  a.mask_out = nullptr;
+  if (f16_products() && !f32) {
+    NOF_HIP(nof::launch_gemm_h(a, ksplit, st_, &v));
+    tally_h(v);
+  } else {
+    NOF_HIP(nof::launch_gemm(a, ksplit, st_, &v));
+    tally(v);
+  }
+  return false;
 }
 
 // split-K of a weight gradient (k = the level's M samples, or its rays): about 1024 workgroups (four per
@@ -909,30 +929,11 @@ void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t 
   a.kchunk = kc; a.slab_stride = (int64_t)nout * ncols;
   float* bias_part = slab + (size_t)ks * nout * ncols;  // the bias gradient's per-chunk sums [ks][nout]
   if (bias_dst) a.rowsum = bias_part;
-  int v;
-  if (scale) {  // F16_PRODUCTS: dZ scaled inside each fp16 product, the partials unscaled
-    a.scale_amax = scale; a.scale_src = 1;
-    NOF_HIP(nof::launch_gemm_h(a, ks, st_, &v));
-    tally_h(v);
-  } else {
-    NOF_HIP(nof::launch_gemm(a, ks, st_, &v));
-    tally(v);
-  }
+  // F16_PRODUCTS: dZ scaled inside each fp16 product, the partials unscaled; without a scale on fp32 k_gemm
+  if (scale) { a.scale_amax = scale; a.scale_src = 1; }
+  gen_product(a, ks, false, !scale);
   wg_jobs_.push_back({slab, dst, a.slab_stride, ld, nout, ncols, ncols, ks, accumulate});
   if (bias_dst) wg_jobs_.push_back({bias_part, bias_dst, nout, nout, 1, nout, nout, ks, accumulate});
-}
-
-bool AcceleratedMLP::gen_gemm(nof::GemmArgs a) {
-  if (!f16_products() && nof::gemm_ws_fits(a)) {
-    int v;
-    NOF_HIP(nof::launch_gemm_ws(a, st_, &v));
-    tally(v);
-    return true;
-  }
-  NOF_REQUIRE(!a.mask_in, "a ReLU-bit mask needs the weight-stationary kernel");
-  a.mask_out = nullptr;
-  gemm1(a);
-  return false;
 }
 
 void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
@@ -959,7 +960,7 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
     a.bias = prm + boff_[l]; a.relu = 1;
     a.C = H(l); a.ci = W; a.cj = 1;
     a.mask_out = MB(l);
-    G.mb_ok[l] = gen_gemm(a);
+    G.mb_ok[l] = gen_product(a, 1, true);
   }
   {  // density head (MLPcs:101): z[:, 0]
     nof::GemmArgs a;
@@ -968,7 +969,7 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
     a.B1 = gsrc(prm + woff_[D], W, 1);
     a.bias = prm + boff_[D];
     a.C = G.z.p; a.ci = 4; a.cj = 1;
-    gen_gemm(a);
+    gen_product(a, 1, true);
   }
   for (int i = 0; i < Dc; ++i) {  // view layer [h | view PE of the ray] (MLPcs:102-106), condition layers
     const int l = D + 1 + i;
@@ -985,7 +986,7 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
     a.bias = prm + boff_[l]; a.relu = 1;
     a.C = Hc(i); a.ci = Wc; a.cj = 1;
     a.mask_out = MB(D + i);
-    G.mb_ok[D + i] = gen_gemm(a);
+    G.mb_ok[D + i] = gen_product(a, 1, true);
   }
   {  // rgb head (MLPcs:107): z[:, 1..3]
     nof::GemmArgs a;
@@ -994,7 +995,7 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
     a.B1 = gsrc(prm + woff_[lr], Wc, 1);
     a.bias = prm + boff_[lr];
     a.C = G.z.p + 1; a.ci = 4; a.cj = 1;
-    gen_gemm(a);
+    gen_product(a, 1, true);
   }
   NOF_HIP(nof::launch_heads_fwd(M, G.z.p, L.sigma.p, L.rgb.p, cfg_.density_bias, rgb_scale(), cfg_.rgb_padding, st_));
   te(kTMlpFwd);
@@ -1026,19 +1027,11 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   auto MB = [&](int l) -> const uint32_t* { return G.mbits.p + (size_t)l * M * 4; };
   // F16_PRODUCTS: the level's delta-scale word; every product with a delta operand scales it (null: no scale)
   const uint32_t* sc = f16_products() ? amax_.p + level : nullptr;
-  // the masking layer's ReLU: its bits where the forward wrote them (mlay: trunk l, condition D + i) and the
-  // weight-stationary kernel fits the product, else the activation `mask` > 0 (k_gemm)
-  auto masked = [&](nof::GemmArgs a, int mlay, const float* mask, int width) {
-    a.mask_in = MB(mlay);
-    if (G.mb_ok[mlay] && nof::gemm_ws_fits(a)) {
-      int v;
-      NOF_HIP(nof::launch_gemm_ws(a, st_, &v));
-      tally(v);
-      return;
-    }
-    a.mask_in = nullptr;
+  // a dX product's mask, the masking layer's ReLU (mlay: trunk l, condition D + i): the activation `mask` > 0, and
+  // its bits where the forward wrote them (gen_product takes one or the other)
+  auto relu_mask = [&](nof::GemmArgs& a, int mlay, const float* mask, int width) {
     a.G = mask; a.gi = width; a.gj = 1;
-    gemm1(a);
+    if (G.mb_ok[mlay]) a.mask_in = MB(mlay);
   };
   // dX of layer l into C, masked by the activation `mask` > 0: C[m][j] = sum_o dZ[m][o] W_l[o][j]
   auto dx = [&](const float* dzp, int64_t ldz, int nout, int l, int mlay, const float* mask, int width, float* C) {
@@ -1049,7 +1042,8 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.B1 = gsrc(prm + woff_[l], 1, in_[l]);
     a.C = C; a.ci = width; a.cj = 1;
     if (sc) { a.scale_amax = sc; a.scale_src = 1; }
-    masked(a, mlay, mask, width);
+    relu_mask(a, mlay, mask, width);
+    gen_product(a, 1, true);
   };
   wg_jobs_.clear();
   wg_off_ = 0;
@@ -1096,7 +1090,8 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.B2 = gsrc(prm + woff_[D], 1, 0);
     a.C = nxt; a.ci = W; a.cj = 1;
     if (sc) { a.scale_amax = sc; a.scale_src = 1; }  // (A2 = dz_density is a delta as well)
-    masked(a, D - 1, H(D - 1), W);
+    relu_mask(a, D - 1, H(D - 1), W);
+    gen_product(a, 1, true);
     std::swap(cur, nxt);
   }
   // stop_level_grad = 0: dEnc = delta_0 W_0 + sum over skip layers s of delta_s W_s[:, W : W + P], two layers per
@@ -1119,7 +1114,7 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.C = parts ? gdenc_part_.p + (size_t)nparts * M * P : gdenc_.p;
     a.ci = P; a.cj = 1;
     if (sc) { a.scale_amax = sc; a.scale_src = 1; }
-    gemm1(a);
+    gen_product(a);
     ++nparts;
   };
   for (int l = D - 1; l >= 0; --l) {  // trunk

@@ -236,10 +236,9 @@ class AcceleratedMLP {
     DevBuf<uint32_t> mbits;
     std::vector<char> mb_ok;
   };
-  // an unsplit product: the weight-stationary kernel where the shape fits it (gemm_ws.hip), else k_gemm;
-  // returns whether the weight-stationary kernel ran
-  bool gen_gemm(nof::GemmArgs a);
-  void gemm1(nof::GemmArgs a);  // k_gemm (k_gemm_h with f16_products()), no split: one k chunk
+  // the one place a GEMM's kernel is chosen and tallied (accelerated.cpp); returns whether the weight-stationary
+  // kernel ran
+  bool gen_product(nof::GemmArgs a, int ksplit = 1, bool ws = false, bool f32 = false);
   uint32_t disp_[nof::kGvCount] = {};
   uint32_t disp_h_[nof::kGhCount] = {};
   void tally(int variant, int launches = 1) { if (variant >= 0) disp_[variant] += (uint32_t)launches; }

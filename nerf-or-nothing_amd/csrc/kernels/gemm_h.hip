@@ -24,6 +24,7 @@
 //     whole rows = 128 consecutive bytes, whatever the chunk order inside a row.
 // Only the row sums (wave 0 of the first column tile, one row per lane) read with 2-way conflicts.
 #include "common.h"
+#include "gemm_tile.h"
 #include "launch.h"
 #include "mlp_common.h"
 
@@ -31,9 +32,7 @@ namespace nof {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kHT = 64;    // tile rows (i)
 constexpr int kHK = 32;    // k-step: one 16x16x32 MFMA deep
-constexpr int kHThreads = 256;
 constexpr int kHD = 2;     // k-steps of global loads in flight
 
 __device__ __forceinline__ int h_chunk(int r, int c) { return c ^ ((r >> 1) & 3); }
@@ -52,7 +51,7 @@ __device__ __forceinline__ int h_chunk(int r, int c) { return c ^ ((r >> 1) & 3)
 // (a source boundary or the chunk's tail inside the step) compute and mask each element.
 template <int T>
 struct HPlan {
-  static constexpr int E = T * kHK / kHThreads;
+  static constexpr int E = T * kHK / kTileThreads;
   static constexpr int P = E / 2;
   const float* b1[P];  // row-fast: [0] alone
   const float* b2[P];
@@ -200,25 +199,20 @@ __device__ __forceinline__ void h_store(uint32_t* dst, const HPlan<T>& pl, const
   }
 }
 
-// tile 64 (i) x TN (j), 4 waves in a 2 x 2 grid of 32 x TN / 2 wave tiles; the C/D lane map of 16x16x32
-// (col = lane & 15, row = 4 (lane >> 4) + reg) is 16x16x4's, so the epilogue is k_gemm's
+// gemm_tile.h's tile and epilogue (k_gemm's) around the fp16 load pipeline above
 template <int TN, bool TWO, bool MASK>
-__global__ __launch_bounds__(kHThreads, 2) void k_gemm_h(GemmArgs a) {
+__global__ __launch_bounds__(kTileThreads, 2) void k_gemm_h(GemmArgs a) {
   static_assert(!MASK || TN == 64, "the mask epilogue is the 64-column tiles'");
   constexpr int NQ = TN / 32;
-  __shared__ __attribute__((aligned(16))) uint32_t As[kHT * 16], Bs[TN * 16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ntc = (a.N + TN - 1) / TN;
-  const int tcol = blockIdx.x % ntc;
-  const int i0 = (blockIdx.x / ntc) * kHT, j0 = tcol * TN;
-  const int wi = (wave >> 1) * 32, wj = (wave & 1) * (TN / 2);
-  const int K = a.K1 + a.K2;
-  const int kb = blockIdx.z * a.kchunk, ke = min(K, kb + a.kchunk);
+  __shared__ __attribute__((aligned(16))) uint32_t As[kTileM * 16], Bs[TN * 16];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const GemmTile t = gemm_tile<TN>(a);
+  const int i0 = t.i0, j0 = t.j0, wi = t.wi, wj = t.wj, kb = t.kb, ke = t.ke;
   // the power-of-two scale of one operand and its exact inverse (wave-uniform: one scalar load)
   const float s = a.scale_src && a.scale_amax ? delta_scale(a.scale_amax, false) : 1.0f;
   const float inv_s = a.scale_src && a.scale_amax ? delta_scale(a.scale_amax, true) : 1.0f;
   const float sa = a.scale_src == 1 ? s : 1.0f, sb = a.scale_src == 2 ? s : 1.0f;
-  HPlan<kHT> pa;
+  HPlan<kTileM> pa;
   HPlan<TN> pb;
   h_plan<TWO>(pa, a.A1, a.A2, a.M, i0, tid, a.K1, kb);
   h_plan<TWO>(pb, a.B1, a.B2, a.N, j0, tid, a.K1, kb);
@@ -227,10 +221,8 @@ __global__ __launch_bounds__(kHThreads, 2) void k_gemm_h(GemmArgs a) {
   for (int p = 0; p < 2; ++p)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[p][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const int ib = i0 + wi + 4 * (lane >> 4), jb = j0 + wj + (lane & 15);
-  const bool rowsum = a.rowsum && tcol == 0 && wave == 0;
   float rs = 0.0f;
-  float va[kHD][HPlan<kHT>::E], vb[kHD][HPlan<TN>::E];
+  float va[kHD][HPlan<kTileM>::E], vb[kHD][HPlan<TN>::E];
   uint32_t oa[kHD], ob[kHD];  // a masked step's element masks
   bool fa[kHD], fb[kHD];      // the set's step took the uniform-offset path (wave-uniform)
 #pragma unroll
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(kHThreads, 2) void k_gemm_h(GemmArgs a) {
       fa[d] = h_fetch<TWO>(va[d], oa[d], pa, a.A1, a.A2, a.K1, ke, k0 + kHD * kHK, a.M, i0, tid);
       fb[d] = h_fetch<TWO>(vb[d], ob[d], pb, a.B1, a.B2, a.K1, ke, k0 + kHD * kHK, a.N, j0, tid);
     }
-    if (rowsum)
+    if (t.rowsum)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const f16x8 w = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(As + lane * 16 + 4 * h_chunk(lane, c)));
@@ -274,43 +266,7 @@ __global__ __launch_bounds__(kHThreads, 2) void k_gemm_h(GemmArgs a) {
 #pragma unroll
     for (int d = 0; d < kHD; ++d)
       if (k0 + d * kHK < ke) step(k0 + d * kHK, d);
-  // the dX products' ReLU mask (G > 0): every load issued before the epilogue uses any (k_gemm)
-  float gv[MASK ? NQ : 1][2][4];
-  if constexpr (MASK) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t i = min(ib + 16 * p + r, a.M - 1), j = min(jb + 16 * q, a.N - 1);
-          gv[q][p][r] = a.G[i * a.gi + j * a.gj];
-        }
-  }
-  if (rowsum && i0 + lane < a.M) a.rowsum[(int64_t)blockIdx.z * a.M + i0 + lane] = rs * inv_s;
-  float* C = a.C + (int64_t)blockIdx.z * a.slab_stride;
-  const int64_t crow = (int64_t)ib * a.ci;
-  float bj[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) bj[q] = a.bias && jb + 16 * q < a.N ? a.bias[jb + 16 * q] : 0.0f;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const int j = jb + 16 * q;
-    if (j >= a.N) continue;
-    const int64_t cj = (int64_t)j * a.cj;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (ib + 16 * p + r >= a.M) continue;
-        float v = acc[p][q][r] * inv_s;
-        if (a.bias) v += bj[q];
-        if (a.relu) v = fmaxf(v, 0.0f);
-        if constexpr (MASK)
-          if (!(gv[q][p][r] > 0.0f)) v = 0.0f;
-        C[crow + (int64_t)(16 * p + r) * a.ci + cj] = v;
-      }
-  }
+  gemm_epilogue<NQ, MASK, true>(a, t, acc, rs, inv_s);
 }
 
 const char* gen_h_variant_name(int v) {
@@ -323,27 +279,16 @@ const char* gen_h_variant_name(int v) {
 hipError_t launch_gemm_h(const GemmArgs& a, int ksplit, hipStream_t st, int* variant) {
   if (variant) *variant = -1;
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (ksplit < 1 || a.kchunk <= 0 || !a.A1.p || !a.B1.p || (a.K2 > 0 && (!a.A2.p || !a.B2.p)) || a.A1.idiv < 1 ||
-      a.A2.idiv < 1 || a.B1.idiv < 1 || a.B2.idiv < 1 || a.scale_src < 0 || a.scale_src > 2 || !a.C)
-    return hipErrorInvalidValue;
-  const bool two = a.K2 > 0, mask = a.G != nullptr;
-  // split-K is the weight gradients': one k source, no mask (the instantiations the any-shape path needs)
-  if (ksplit > 1 && (two || mask)) return hipErrorInvalidValue;
-  const bool wide = a.N > 64 && ksplit > 1;  // 64 x 128 tiles: A read once for up to 128 columns (launch_gemm)
-  const int TN = wide ? 128 : 64;
-  const int64_t tiles = (int64_t)((a.N + TN - 1) / TN) * ((a.M + kHT - 1) / kHT);
-  if (tiles > 0x7fffffff || ksplit > 65535) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)tiles, 1, ksplit);
-  auto go = [&](auto kern, int v) {
-    if (variant) *variant = v;
-    hipLaunchKernelGGL(kern, grid, dim3(kHThreads), 0, st, a);
-  };
-  if (wide) go(k_gemm_h<128, false, false>, kGhGemm128Split);
-  else if (ksplit > 1) go(k_gemm_h<64, false, false>, kGhGemm64Split);
-  else if (two && mask) go(k_gemm_h<64, true, true>, kGhGemm64 + 3);
-  else if (mask) go(k_gemm_h<64, false, true>, kGhGemm64 + 2);
-  else if (two) go(k_gemm_h<64, true, false>, kGhGemm64 + 1);
-  else go(k_gemm_h<64, false, false>, kGhGemm64);
+  if (a.scale_src < 0 || a.scale_src > 2) return hipErrorInvalidValue;
+  static constexpr void (*kKern[])(GemmArgs) = {k_gemm_h<64, false, false>, k_gemm_h<64, true, false>,
+                                                k_gemm_h<64, false, true>,  k_gemm_h<64, true, true>,
+                                                k_gemm_h<64, false, false>, k_gemm_h<128, false, false>};
+  int pick;
+  dim3 grid;
+  const hipError_t e = gemm_tile_grid(a, ksplit, &pick, &grid);
+  if (e != hipSuccess) return e;
+  if (variant) *variant = kGhGemm64 + pick;
+  hipLaunchKernelGGL(kKern[pick], grid, dim3(kTileThreads), 0, st, a);
   return hipGetLastError();
 }
 

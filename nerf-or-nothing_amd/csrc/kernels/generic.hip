@@ -17,15 +17,14 @@
 //     the heads (MNcs:19-28, 151-152, 184-189).
 // Numerics: fp32 products in k order (the MFMA's fmaf chain) — the fp32 mode's 1e-5 contract.
 #include "common.h"
+#include "gemm_tile.h"
 #include "geometry.h"
 #include "launch.h"
 
 namespace nof {
 
-constexpr int kGT = 64;   // tile edge
 constexpr int kGK = 16;   // k-step
 constexpr int kGS = 24;   // LDS row stride of a [row][k] tile (floats): conflict-free 16-byte operand reads
-constexpr int kGThreads = 256;
 
 // Per-thread load plan of one operand tile (T rows x 16 k per k-step, E = T / 16 elements per thread).
 // Threads run along the source's unit-stride index (coalesced): k when kfast (sk == 1), else the row
@@ -39,7 +38,7 @@ constexpr int kGThreads = 256;
 // step are issued unconditionally, so they are in flight together and overlap the previous step's MFMAs.
 template <int T>
 struct GPlan {
-  static constexpr int E = T * kGK / kGThreads;
+  static constexpr int E = T * kGK / kTileThreads;
   const float* b1[E];  // source-1 / source-2 element pointers at k = 0 (row base + kl sk)
   const float* b2[E];
   int r[E], kl[E];     // tile row, k within the step
@@ -54,7 +53,7 @@ __device__ __forceinline__ void g_plan(GPlan<T>& pl, const GemmSrc& s1, const Ge
   pl.kfast = kfast;
 #pragma unroll
   for (int e = 0; e < GPlan<T>::E; ++e) {
-    const int q = e * kGThreads + tid;
+    const int q = e * kTileThreads + tid;
     pl.r[e] = kfast ? q / kGK : tid % T;
     pl.kl[e] = kfast ? q % kGK : (tid / T) * GPlan<T>::E + e;
     const int i = r0 + pl.r[e];
@@ -123,28 +122,22 @@ __device__ __forceinline__ void g_store(float (*dst)[kGS], const GPlan<T>& pl, c
   }
 }
 
-// tile 64 (i) x TN (j), TN = 64 or 128; 4 waves in a 2 x 2 grid of 32 x TN/2 wave tiles.  Launch bounds
+// gemm_tile.h's tile and epilogue around the fp32 load pipeline above.  Launch bounds
 // (256, 2): at least two waves per SIMD, so the accumulators live in VGPRs, not AGPRs (no accvgpr copies;
 // measured configs[0] step 6.52 -> 6.41 ms; k-steps of 32 instead of 16: 7.42 ms, and 9.59 ms against
 // 6.32 ms once the loads run two k-steps ahead: 256 VGPRs, so the occupancy falls to two waves per SIMD)
 template <int TN, bool TWO, bool MASK>  // MASK: the dX GEMMs' ReLU-mask epilogue (a.G), 64-column tiles only
-__global__ __launch_bounds__(kGThreads, 2) void k_gemm(GemmArgs a) {
+__global__ __launch_bounds__(kTileThreads, 2) void k_gemm(GemmArgs a) {
   static_assert(!MASK || TN == 64, "the mask epilogue is the 64-column tiles'");
   constexpr int NQ = TN / 32;  // 16-wide MFMA tiles per wave along j
   // k-steps of loads in flight: 3 or 4 at TN 64 (116 / 124 VGPRs, occupancy unchanged) ran the configs[0]
   // step 6.23 -> 6.40 / 6.44 ms; 3 at TN 128 takes 175 VGPRs (two waves per SIMD)
   constexpr int kGD = 2;
-  __shared__ __attribute__((aligned(16))) float As[kGT][kGS], Bs[TN][kGS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // output tiles linear in blockIdx.x, columns fastest (a grid's y is capped at 65535 row tiles)
-  const int ntc = (a.N + TN - 1) / TN;
-  const int tcol = blockIdx.x % ntc;
-  const int i0 = (blockIdx.x / ntc) * kGT, j0 = tcol * TN;
-  const int wi = (wave >> 1) * 32, wj = (wave & 1) * (TN / 2);
-  const int K = a.K1 + a.K2;
-  // the chunk end bounds k as well (a split-K chunk reads only its own k)
-  const int kb = blockIdx.z * a.kchunk, ke = min(K, kb + a.kchunk);
-  GPlan<kGT> pa;
+  __shared__ __attribute__((aligned(16))) float As[kTileM][kGS], Bs[TN][kGS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const GemmTile t = gemm_tile<TN>(a);
+  const int i0 = t.i0, j0 = t.j0, wi = t.wi, wj = t.wj, kb = t.kb, ke = t.ke;
+  GPlan<kTileM> pa;
   GPlan<TN> pb;
   g_plan<TWO>(pa, a.A1, a.A2, a.M, i0, tid);
   g_plan<TWO>(pb, a.B1, a.B2, a.N, j0, tid);
@@ -153,17 +146,12 @@ __global__ __launch_bounds__(kGThreads, 2) void k_gemm(GemmArgs a) {
   for (int p = 0; p < 2; ++p)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[p][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  // lane rows i = ib + 16 p + r, columns j = jb + 16 q (the epilogue's)
-  const int ib = i0 + wi + 4 * (lane >> 4), jb = j0 + wj + (lane & 15);
-  // row sums of A over this chunk's k (the bias gradient beside a weight gradient): the first column
-  // tile's wave 0, one row per lane, from the LDS tile, in k order
-  const bool rowsum = a.rowsum && tcol == 0 && wave == 0;
   float rs = 0.0f;
   // kGD k-steps of loads in flight: set s holds the steps = s mod kGD; a step's loads are issued kGD steps
   // ahead of their LDS store (one step ahead left the global-load latency exposed: the loop is
   // latency-bound, not MFMA- or HBM-bound)
-  float va[kGD][GPlan<kGT>::E], vb[kGD][GPlan<TN>::E];
-  bool oa[kGD][GPlan<kGT>::E], ob[kGD][GPlan<TN>::E];
+  float va[kGD][GPlan<kTileM>::E], vb[kGD][GPlan<TN>::E];
+  bool oa[kGD][GPlan<kTileM>::E], ob[kGD][GPlan<TN>::E];
   bool fa[kGD], fb[kGD];  // the set's step took the uniform-offset path (wave-uniform)
 #pragma unroll
   for (int s = 0; s < kGD; ++s) {
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(kGThreads, 2) void k_gemm(GemmArgs a) {
       fa[s] = g_fetch<TWO>(va[s], oa[s], pa, a.A1, a.A2, a.K1, ke, k0 + kGD * kGK);
       fb[s] = g_fetch<TWO>(vb[s], ob[s], pb, a.B1, a.B2, a.K1, ke, k0 + kGD * kGK);
     }
-    if (rowsum)
+    if (t.rowsum)
 #pragma unroll
       for (int u = 0; u < kGK / 4; ++u) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(&As[lane][4 * u]);
@@ -205,47 +193,7 @@ __global__ __launch_bounds__(kGThreads, 2) void k_gemm(GemmArgs a) {
 #pragma unroll
     for (int s = 0; s < kGD; ++s)
       if (k0 + s * kGK < ke) step(k0 + s * kGK, s);
-  // the dX GEMMs' ReLU mask (G > 0: the forward activation): all 16 loads issued together before the
-  // epilogue uses any (per element, beside its use, they were dependent loads one after another: the dX
-  // GEMMs 200 us against 136 us for forward GEMMs of the same shape; configs[0] step 5.16 -> 4.72 ms).
-  // Issued before the k loop instead they held 16 more registers through it: a wave per SIMD less, 10 % slower
-  float gv[MASK ? NQ : 1][2][4];
-  if constexpr (MASK) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t i = min(ib + 16 * p + r, a.M - 1), j = min(jb + 16 * q, a.N - 1);
-          gv[q][p][r] = a.G[i * a.gi + j * a.gj];
-        }
-  }
-  if (rowsum && i0 + lane < a.M) a.rowsum[(int64_t)blockIdx.z * a.M + i0 + lane] = rs;
-  float* C = a.C + (int64_t)blockIdx.z * a.slab_stride;
-  // one 64-bit row offset per lane, wave-uniform steps
-  const int64_t crow = (int64_t)ib * a.ci;
-  float bj[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) bj[q] = a.bias && jb + 16 * q < a.N ? a.bias[jb + 16 * q] : 0.0f;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const int j = jb + 16 * q;
-    if (j >= a.N) continue;
-    const int64_t cj = (int64_t)j * a.cj;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (ib + 16 * p + r >= a.M) continue;
-        float v = acc[p][q][r];
-        if (a.bias) v += bj[q];
-        if (a.relu) v = fmaxf(v, 0.0f);
-        if constexpr (MASK)
-          if (!(gv[q][p][r] > 0.0f)) v = 0.0f;
-        C[crow + (int64_t)(16 * p + r) * a.ci + cj] = v;
-      }
-  }
+  gemm_epilogue<NQ, MASK, false>(a, t, acc, rs);
 }
 
 // dst[r ld + c] (+)= sum over slabs z = 0 .. nz - 1 of slabs[z][r pitch + c] (z order within each of 4
@@ -386,9 +334,8 @@ __global__ void k_heads_bwd(int M, const float* __restrict__ dsigma, const float
 const char* gen_variant_name(int v) {
   static const char* const kNames[kGvCount] = {
       "k_gemm<64,false,false>.unsplit", "k_gemm<64,true,false>.unsplit", "k_gemm<64,false,true>.unsplit",
-      "k_gemm<64,true,true>.unsplit", "k_gemm<64,false,false>.splitk", "k_gemm<64,true,false>.splitk",
-      "k_gemm<64,false,true>.splitk", "k_gemm<64,true,true>.splitk", "k_gemm<128,false,false>.splitk",
-      "k_gemm<128,true,false>.splitk", "k_gemm_ws<8,6,0,false>", "k_gemm_ws<8,8,0,false>", "k_gemm_ws<1,8,0,false>",
+      "k_gemm<64,true,true>.unsplit", "k_gemm<64,false,false>.splitk", "k_gemm<128,false,false>.splitk",
+      "k_gemm_ws<8,6,0,false>", "k_gemm_ws<8,8,0,false>", "k_gemm_ws<1,8,0,false>",
       "k_gemm_ws<8,8,2,false>", "k_gemm_ws<8,8,1,false>", "k_gemm_ws<8,1,0,false,true>", "k_gemm_ws<1>",
       "k_gemm_ws<2>", "k_gemm_ws<3>", "k_gemm_ws<4>", "k_gemm_ws<5>", "k_gemm_ws<6>", "k_gemm_ws<7>", "k_gemm_ws<8>",
       "k_encode_g", "k_encode_g4", "k_slab_sums", "k_ray_sum"};
@@ -398,36 +345,19 @@ const char* gen_variant_name(int v) {
 hipError_t launch_gemm(const GemmArgs& a, int ksplit, hipStream_t st, int* variant) {
   if (variant) *variant = -1;
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (ksplit < 1 || a.kchunk <= 0 || a.kchunk % kGK != 0 || !a.A1.p || !a.B1.p || (a.K2 > 0 && (!a.A2.p || !a.B2.p)) ||
-      a.A1.idiv < 1 || a.A2.idiv < 1 || a.B1.idiv < 1 || a.B2.idiv < 1)
-    return hipErrorInvalidValue;
-  // 64 x 128 tiles for split-K weight gradients wider than 64 (A read once for up to 128 columns; measured
-  // 5 % faster there, 10 % slower on the unsplit dX GEMMs).  Measured and not kept: 128 x 128 tiles (two
-  // waves per SIMD) ran the trunk dX / dW GEMMs 185 -> 260 / 158 -> 230 us (the loop is latency-bound:
-  // occupancy wins), and addresses recomputed per k-step instead of per-element row pointers 6.52 -> 6.84
-  // ms per configs[0] step
-  const bool wide = a.N > 64 && ksplit > 1;
-  if (wide && a.G) return hipErrorInvalidValue;  // the mask epilogue is the 64-column tiles' (k_gemm)
-  const int TN = wide ? 128 : 64;
-  const int64_t tiles = (int64_t)((a.N + TN - 1) / TN) * ((a.M + kGT - 1) / kGT);
-  if (tiles > 0x7fffffff || ksplit > 65535) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)tiles, 1, ksplit);
-  const bool two = a.K2 > 0;
-  auto go = [&](auto kern, int v) {
-    if (variant) *variant = v;
-    hipLaunchKernelGGL(kern, grid, dim3(kGThreads), 0, st, a);
-  };
-  const bool mask = a.G != nullptr;
-  const int v64 = ksplit > 1 ? kGvGemm64Split : kGvGemm64;
-  if (two) {
-    if (wide) go(k_gemm<128, true, false>, kGvGemm128Split + 1);
-    else if (mask) go(k_gemm<64, true, true>, v64 + 3);
-    else go(k_gemm<64, true, false>, v64 + 1);
-  } else {
-    if (wide) go(k_gemm<128, false, false>, kGvGemm128Split);
-    else if (mask) go(k_gemm<64, false, true>, v64 + 2);
-    else go(k_gemm<64, false, false>, v64);
-  }
+  if (a.kchunk % kGK != 0) return hipErrorInvalidValue;
+  // 64 x 128 tiles for split-K weight gradients wider than 64: measured 5 % faster there, 10 % slower on the
+  // unsplit dX GEMMs.  Measured and not kept: 128 x 128 tiles (two waves per SIMD) ran the trunk dX / dW GEMMs
+  // 185 -> 260 / 158 -> 230 us (the loop is latency-bound: occupancy wins), and addresses recomputed per k-step
+  // instead of per-element row pointers 6.52 -> 6.84 ms per configs[0] step
+  static constexpr void (*kKern[])(GemmArgs) = {k_gemm<64, false, false>, k_gemm<64, true, false>, k_gemm<64, false, true>,
+                                                k_gemm<64, true, true>,   k_gemm<64, false, false>, k_gemm<128, false, false>};
+  int pick;
+  dim3 grid;
+  const hipError_t e = gemm_tile_grid(a, ksplit, &pick, &grid);
+  if (e != hipSuccess) return e;
+  if (variant) *variant = kGvGemm64 + pick;
+  hipLaunchKernelGGL(kKern[pick], grid, dim3(kTileThreads), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_slab_sums(const SlabJob* jobs, int n, hipStream_t st, int* launches) {

@@ -235,7 +235,8 @@ struct GemmSrc {
 };
 // C(i, j) = epilogue(sum_{k < K1 + K2} A(i, k) B(j, k)), i < M, j < N; A(i, k) = A1(i, k) for k < K1, else
 // A2(i, k - K1) (B alike).  Epilogue: + bias[j], ReLU, then 0 where !(G(i, j) > 0) — each optional.
-// Split-K: blockIdx.z = chunk of kchunk (a multiple of 16) k values, its raw sums at C + z slab_stride.
+// Split-K (one k source, no G): blockIdx.z = chunk of kchunk (a multiple of 16) k values, its raw sums at C + z
+// slab_stride.
 struct GemmArgs {
   int M = 0, N = 0, K1 = 0, K2 = 0;
   GemmSrc A1, A2, B1, B2;
@@ -258,20 +259,20 @@ struct GemmArgs {
 // tooling see which instantiation a product ran on).  A launcher reports its pick through its optional
 // `variant` out-parameter, set where the template is chosen (-1: nothing launched).
 enum GenVariant : int {
-  kGvGemm64 = 0,        // k_gemm<64, TWO, MASK>, one k chunk: + TWO + 2 MASK
-  kGvGemm64Split = 4,   // ... split-K (ksplit > 1): + TWO + 2 MASK
-  kGvGemm128Split = 8,  // k_gemm<128, TWO, false> (split-K only): + TWO
-  kGvWs_8_6_0 = 10,     // k_gemm_ws's static chunk shapes <NT, SC1, SC2, SV2[, T1]>
+  kGvGemm64 = 0,       // k_gemm<64, TWO, MASK>, one k chunk: + TWO + 2 MASK
+  kGvGemm64Split = 4,  // k_gemm<64, false, false>, split-K (ksplit > 1)
+  kGvGemm128Split,     // k_gemm<128, false, false>, split-K, N > 64
+  kGvWs_8_6_0,         // k_gemm_ws's static chunk shapes <NT, SC1, SC2, SV2[, T1]>
   kGvWs_8_8_0,
   kGvWs_1_8_0,
   kGvWs_8_8_2,
   kGvWs_8_8_1,
   kGvWs_8_1_0_T1,
-  kGvWsRuntime = 16,    // k_gemm_ws<NT>, runtime chunk shape: + NT - 1 (NT = 1 .. 8)
-  kGvEncode = 24,       // k_encode_g
-  kGvEncode4,           // k_encode_g4
-  kGvSlabSums,          // k_slab_sums (one count per batch launched)
-  kGvRaySum,            // k_ray_sum
+  kGvWsRuntime,                  // k_gemm_ws<NT>, runtime chunk shape: + NT - 1 (NT = 1 .. 8)
+  kGvEncode = kGvWsRuntime + 8,  // k_encode_g
+  kGvEncode4,                    // k_encode_g4
+  kGvSlabSums,                   // k_slab_sums (one count per batch launched)
+  kGvRaySum,                     // k_ray_sum
   kGvCount
 };
 const char* gen_variant_name(int v);  // null outside [0, kGvCount)

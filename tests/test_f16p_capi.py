@@ -39,7 +39,7 @@ def test_gen_dispatch_h_name_list():
     n = C.c_int32()
     assert lib.nof_mlp_gen_dispatch_h(None, 0, None, 0, C.byref(n)) == 1
     assert hasattr(nof.AcceleratedMLP, "gen_dispatch_h")
-    assert not set(names) & set(nof.gen_dispatch_names()) and len(nof.gen_dispatch_names()) == 28
+    assert not set(names) & set(nof.gen_dispatch_names()) and len(nof.gen_dispatch_names()) == 24
 
 
 def test_kernel_gemm_h_refuses_bad_arguments():

@@ -106,14 +106,7 @@ DISPATCH = {
     "nt8_runtime": ("k_encode_g4", "k_gemm_ws<1>", "k_gemm_ws<5>", "k_gemm_ws<8>", _G128S, _G64S, _G64, *_SUMS),
     "grid_2x30_1x14" + MANY_RAYS: ("k_encode_g4", "k_gemm_ws<2>", *_K_GEMM_UNSPLIT, _G64S, *_SUMS),
 }
-# variants of the name list that no accepted configuration reaches, each with its reason
-UNREACHED = {
-    # launch_gemm would run them, but its only split-K caller is gen_wgrad: one source (K2 = 0), no mask (G)
-    "k_gemm<64,true,false>.splitk": "split-K is the weight gradients' alone: one k source",
-    "k_gemm<128,true,false>.splitk": "split-K is the weight gradients' alone: one k source",
-    "k_gemm<64,false,true>.splitk": "split-K is the weight gradients' alone: no ReLU-mask epilogue",
-    "k_gemm<64,true,true>.splitk": "split-K is the weight gradients' alone: no ReLU-mask epilogue",
-}
+UNREACHED = {}  # every name is reached
 
 
 def _cfg(spec):
