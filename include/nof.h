@@ -222,6 +222,17 @@ nof_status nof_mipnerf_level_view(nof_mipnerf* h, int32_t level, nof_level_view*
  * dL/dt^level [n][S + 1] = integrator + encoding + bin-edge terms (NULL for level 0, whose t is a constant).
  * Both NULL with stop_level_grad = 1. */
 nof_status nof_mipnerf_cross_view(nof_mipnerf* h, int32_t level, const float** w_grad, const float** t_grad);
+/* Ray gradients, for camera refinement: with the option on, every step also leaves dL/d origins and
+ * dL/d directions of its own rays (radius, near, far, the t-values and the Philox uniforms held constant).
+ * Any-shape objects only (any network in F32 / F16_PRODUCTS; the reference 8x256 in F16_PRODUCTS, or in F32 with
+ * stop_level_grad = 0); a fused 8x256 object: NOF_ERR_UNSUPPORTED, the object staying usable.  Allocates; call
+ * before the step.  enable = 0 frees nothing and launches nothing more.  The parameter gradients are bitwise the
+ * same with the option on or off. */
+nof_status nof_mipnerf_set_ray_grad(nof_mipnerf* h, int32_t enable);
+/* the last step's dL/d origins, dL/d directions [n][3], borrowed device pointers (overwritten by the next step;
+ * with NOF_GRAD_ACCUMULATE too: they belong to the call's own rays); NOF_ERR_INVALID_ARG before a step with the
+ * option on */
+nof_status nof_mipnerf_ray_grad(nof_mipnerf* h, const float** dev_o_grad, const float** dev_d_grad);
 /* sum over rays and levels of lambda_l * m_r |C - p|^2 / sum m (fused path only; synchronises) */
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
@@ -469,6 +480,18 @@ nof_status nof_dataset_scene_info(nof_dataset* ds, int32_t* num_views, int32_t* 
 nof_status nof_dataset_render_view(nof_dataset* ds, nof_mipnerf* model, int32_t view, const float* host_pose,
                                    int32_t scale, uint32_t flags, const nof_view_out* out,
                                    nof_view_metrics* metrics);
+/* Camera refinement.  Image-backed, ndc = 0: the gradients [n][3] of the rays of the dataset's LAST
+ * nof_dataset_next batch (its record_index; n at most that batch's) summed per view -> dev_pose_grad [V][12]
+ * (rotation row-major, then translation; d = R cam, o = t, the radius held constant).  accumulate = 0 overwrites
+ * (a view that drew no ray: 0), else adds (such a view's row is left as it is).  Bitwise repeatable.
+ * NOF_ERR_UNSUPPORTED: not image-backed, or an NDC scene (ConvertToNdc is not differentiated here). */
+nof_status nof_dataset_pose_grad(nof_dataset* ds, int32_t n, const float* dev_o_grad, const float* dev_d_grad,
+                                 float* dev_pose_grad, int32_t accumulate, void* stream);
+/* the image-backed dataset's pose table, V x 12 host floats.  set: ordered with the dataset's next gather and with
+ * nof_dataset_render_view (it waits for the device, then copies); rays are made from the table inside the
+ * gather, so nothing is regenerated. */
+nof_status nof_dataset_get_poses(nof_dataset* ds, float* host_poses);
+nof_status nof_dataset_set_poses(nof_dataset* ds, const float* host_poses);
 
 /* ---- AcceleratedMLP (AcceleratedMLP.h:7-45) -------------------------------------------------- */
 /* get_output MLPcpp:214-255: encoded inputs in device memory (enc_pos [n*S][96] in the reference's
@@ -639,6 +662,16 @@ nof_status nof_kernel_encode_grad(int32_t n, int32_t samples, const float* t, co
                                   const float* dirs, const float* radii, int32_t ray_shape, int32_t min_deg,
                                   int32_t max_deg, const float* dev_enc_pos, const float* dev_enc_pos_grad,
                                   float* dev_t_grad, void* stream);
+/* One level's share of the ray gradients (k_ray_grad, for parity tests): encodings as nof_kernel_encode_grad;
+ * sigma / sigma_grad [n S] (the integrator's |d|: alpha = 1 - exp(-sigma delta |d|)); dev_enc_dir /
+ * dev_enc_dir_grad [n][3 + 6 deg_view] (enc_dir_grad NULL: no view term) -> dev_o_grad, dev_d_grad [n][3],
+ * overwritten, or added to when accumulate.  S a multiple of 32, at most 512. */
+nof_status nof_kernel_ray_grad(int32_t n, int32_t samples, const float* t, const float* origins, const float* dirs,
+                               const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                               const float* dev_enc_pos, const float* dev_enc_pos_grad, const float* sigma,
+                               const float* sigma_grad, int32_t deg_view, const float* dev_enc_dir,
+                               const float* dev_enc_dir_grad, int32_t accumulate, float* dev_o_grad,
+                               float* dev_d_grad, void* stream);
 nof_status nof_kernel_adam(int64_t n, float* params, const float* grads, float* m, float* v, float lr,
                            int32_t iteration, void* stream);
 

@@ -232,6 +232,12 @@ nof_status nof_mipnerf_level_view(nof_mipnerf* h, int32_t level, nof_level_view*
 nof_status nof_mipnerf_cross_view(nof_mipnerf* h, int32_t level, const float** w_grad, const float** t_grad) {
   return guard([&] { ARG(h && w_grad && t_grad); h->impl->cross_view(level, w_grad, t_grad); });
 }
+nof_status nof_mipnerf_set_ray_grad(nof_mipnerf* h, int32_t enable) {
+  return guard([&] { ARG(h && (enable == 0 || enable == 1)); DEV(h); h->impl->set_ray_grad(enable != 0); });
+}
+nof_status nof_mipnerf_ray_grad(nof_mipnerf* h, const float** dev_o_grad, const float** dev_d_grad) {
+  return guard([&] { ARG(h && dev_o_grad && dev_d_grad); h->impl->ray_grad(dev_o_grad, dev_d_grad); });
+}
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out) {
   return guard([&] { ARG(h && out); DEV(h); *out = h->impl->loss(); });
 }
@@ -363,6 +369,20 @@ nof_status nof_dataset_render_view(nof_dataset* ds, nof_mipnerf* model, int32_t 
     KEEP_DEVICE;  // render_view selects the dataset's device once its arguments have passed
     ds->impl->render_view(*model->impl, view, host_pose, scale, *out, metrics, flags);
   });
+}
+nof_status nof_dataset_pose_grad(nof_dataset* ds, int32_t n, const float* dev_o_grad, const float* dev_d_grad,
+                                 float* dev_pose_grad, int32_t accumulate, void* stream) {
+  return guard([&] {
+    ARG(ds && dev_o_grad && dev_d_grad && dev_pose_grad);
+    KEEP_DEVICE;  // (pose_grad selects the dataset's device once its arguments have passed)
+    ds->impl->pose_grad(n, dev_o_grad, dev_d_grad, dev_pose_grad, accumulate, (hipStream_t)stream);
+  });
+}
+nof_status nof_dataset_get_poses(nof_dataset* ds, float* host_poses) {
+  return guard([&] { ARG(ds && host_poses); KEEP_DEVICE; ds->impl->get_poses(host_poses); });
+}
+nof_status nof_dataset_set_poses(nof_dataset* ds, const float* host_poses) {
+  return guard([&] { ARG(ds && host_poses); KEEP_DEVICE; ds->impl->set_poses(host_poses); });
 }
 nof_status nof_recenter_poses(float* poses, int32_t V) {
   return guard([&] { recenter_poses(poses, V); });
@@ -762,6 +782,26 @@ nof_status nof_kernel_encode_grad(int32_t n, int32_t S, const float* t, const fl
     a.cylinder = ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
     a.t = t; a.o = o; a.d = d; a.radius = radii; a.enc = enc; a.denc = denc; a.t_grad = t_grad;
     NOF_HIP(nof::launch_encode_grad(a, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_ray_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* radii,
+                               int32_t ray_shape, int32_t min_deg, int32_t max_deg, const float* enc,
+                               const float* denc, const float* sigma, const float* dsigma, int32_t deg_view,
+                               const float* enc_dir, const float* ddir, int32_t accumulate, float* o_grad,
+                               float* d_grad, void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && S >= 32 && S <= 512 && S % 32 == 0 && t && o && d && radii && enc && denc && sigma && dsigma &&
+        o_grad && d_grad);
+    ARG((ray_shape == NOF_RAY_CONICAL || ray_shape == NOF_RAY_CYLINDRICAL) && min_deg >= 0 && max_deg > min_deg &&
+        max_deg <= 24);
+    ARG(!ddir || (enc_dir && deg_view >= 0 && deg_view <= 24));
+    nof::RayGradArgs a{};
+    a.n = n; a.S = S; a.P = 6 * (max_deg - min_deg); a.min_deg = min_deg;
+    a.cylinder = ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    a.Vd = 3 + 6 * deg_view; a.accumulate = accumulate ? 1 : 0;
+    a.t = t; a.o = o; a.d = d; a.radius = radii; a.enc = enc; a.denc = denc; a.sigma = sigma; a.dsigma = dsigma;
+    a.enc_dir = enc_dir; a.ddir = ddir; a.o_grad = o_grad; a.d_grad = d_grad;
+    NOF_HIP(nof::launch_ray_grad(a, (hipStream_t)stream));
   });
 }
 nof_status nof_kernel_adam(int64_t n, float* p, const float* g, float* m, float* v, float lr, int32_t it,

@@ -878,15 +878,7 @@ void AcceleratedMLP::gen_alloc() {
   gd1_.alloc((size_t)max_M_ * Wm);
   gdz_.alloc((size_t)max_M_ * 4);
   gray_.alloc((size_t)cfg_.max_rays * gWc_);
-  if (cross_) {  // levels >= 1 only
-    size_t Mx = 0;
-    for (int l = 1; l < NL; ++l) Mx = std::max(Mx, (size_t)lv_[l].cap);
-    int contrib = 1;  // layer 0 and the skip layers
-    for (int l = 1; l < gD_; ++l) contrib += l % gskip_ == 0 ? 1 : 0;
-    gd2_.alloc(Mx * gW_);
-    gdenc_.alloc(Mx * gP_);
-    if (contrib > 2) gdenc_part_.alloc((size_t)((contrib + 1) / 2) * Mx * gP_);
-  }
+  if (cross_) denc_alloc(1);  // levels >= 1 only
   if (f16_products()) {
     amax_.alloc(NL);
     NOF_HIP(hipMemset(amax_.p, 0, NL * sizeof(uint32_t)));
@@ -907,6 +899,36 @@ void AcceleratedMLP::gen_alloc() {
   }
   wg_need_ = nullptr;
   gslab_.alloc(std::max<size_t>(slab, 1));
+}
+
+void AcceleratedMLP::denc_alloc(int first_level) {
+  size_t Mx = 0;
+  for (int l = first_level; l < (int)lv_.size(); ++l) Mx = std::max(Mx, (size_t)lv_[l].cap);
+  int contrib = 1;  // layer 0 and the skip layers
+  for (int l = 1; l < gD_; ++l) contrib += l % gskip_ == 0 ? 1 : 0;
+  const size_t parts = contrib > 2 ? (size_t)((contrib + 1) / 2) : 0;
+  if (gd2_.n >= Mx * gW_ && gdenc_.n >= Mx * gP_ && gdenc_part_.n >= parts * Mx * gP_) return;
+  if (gd2_.p) NOF_HIP(hipStreamSynchronize(st_));  // (grown after construction: a step may still read them)
+  gd2_.alloc(Mx * gW_);
+  gdenc_.alloc(Mx * gP_);
+  if (parts) gdenc_part_.alloc(parts * Mx * gP_);
+}
+
+void AcceleratedMLP::set_ray_grad(bool on) {
+  if (on) {
+    if (!generic_)
+      throw Error(NOF_ERR_UNSUPPORTED,
+                  "ray gradients need the any-shape path: the fused 8x256 kernels produce no gradient of the encoded "
+                  "input (use NOF_PRECISION_F16_PRODUCTS, or NOF_PRECISION_F32 with stop_level_grad = 0)");
+    denc_alloc(0);  // level 0's dEnc too
+    if (!gddir_.p) {
+      gddir_.alloc((size_t)cfg_.max_rays * gVd_);
+      rg_o_.alloc(3 * (size_t)cfg_.max_rays);
+      rg_d_.alloc(3 * (size_t)cfg_.max_rays);
+    }
+  }
+  ray_grad_ = on;
+  rg_job_ = RayGradJob();
 }
 
 void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t ldz, int nout, nof::GemmSrc x,
@@ -1017,6 +1039,9 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   GenLevel& G = gl_[level];
   const bool dry = wg_need_ != nullptr;  // slab sizing (gen_alloc): only gen_wgrad's records, no launches
   NOF_REQUIRE(dry || (G.ep && G.ed), "get_gradient before get_output for this level");
+  const bool rays = !dry && ray_grad_ && rg_job_.n > 0;  // the owner's step wants dL/do, dL/dd (set_ray_grad)
+  NOF_REQUIRE(!rays || (rg_job_.n == L.n && rg_job_.t[level]), "the ray-gradient job is not this step's");
+  want_denc = want_denc || rays;
   const int M = L.M, S = L.S, D = gD_, W = gW_, Dc = gDc_, Wc = gWc_, P = gP_, Vd = gVd_, lr = D + 1 + Dc;
   const float* prm = params_.p;
   float* gr = grads_.p;
@@ -1077,6 +1102,14 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   if (!dry) {
     NOF_HIP(nof::launch_ray_sum(M / S, S, Wc, cur, Wc, gray_.p, st_));
     tally(nof::kGvRaySum);
+    if (rays) {  // dDir[r][f] = sum_o gray[r][o] W_view[o][W + f]: the per-ray deltas are unscaled fp32 in every mode
+      nof::GemmArgs a;
+      a.M = M / S; a.N = Vd; a.K1 = Wc;
+      a.A1 = gsrc(gray_.p, Wc, 1);
+      a.B1 = gsrc(prm + woff_[D + 1] + W, 1, W + Vd);
+      a.C = gddir_.p; a.ci = Vd; a.cj = 1;
+      gen_product(a, 1, false, true);
+    }
   }
   gen_wgrad(gr + woff_[D + 1] + W, W + Vd, gray_.p, Wc, Wc, gsrc(G.ed, 1, Vd), Vd, M / S, acc);
   // density head
@@ -1158,6 +1191,18 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     NOF_HIP(nof::launch_slab_sums(wg_jobs_.data(), (int)wg_jobs_.size(), st_, &batches));
     tally(nof::kGvSlabSums, batches);
     te(kTMlpBwd);
+  }
+  if (rays) {  // before the next level's backward overwrites dEnc, the per-ray deltas and dDir
+    nof::RayGradArgs ra{};
+    ra.n = L.n; ra.S = S; ra.P = P; ra.min_deg = gmin_deg_; ra.Vd = Vd;
+    ra.cylinder = cfg_.ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    ra.accumulate = rg_job_.first ? 0 : 1;
+    ra.t = rg_job_.t[level]; ra.o = rg_job_.o; ra.d = rg_job_.d; ra.radius = rg_job_.radius;
+    ra.enc = G.ep; ra.denc = gdenc_.p; ra.sigma = L.sigma.p; ra.dsigma = density_grad;
+    ra.enc_dir = G.ed; ra.ddir = gddir_.p;
+    ra.o_grad = rg_o_.p; ra.d_grad = rg_d_.p;
+    NOF_HIP(nof::launch_ray_grad(ra, st_));
+    rg_job_.first = false;
   }
   wg_jobs_.clear();
 }
@@ -1278,6 +1323,18 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     }
     if (lv + 1 < L || cb) timer.end(kTRenderFwd);
   }
+  // ray gradients: every level's backward below is followed by its k_ray_grad (AcceleratedMLP::RayGradJob)
+  struct JobScope {
+    AcceleratedMLP* m;
+    ~JobScope() { m->set_ray_grad_job(nullptr); }
+  } job_scope{mlp};
+  if (mlp->ray_grad()) {
+    AcceleratedMLP::RayGradJob job;
+    job.n = n; job.o = o; job.d = d; job.radius = radii;
+    for (int lv = 0; lv < L; ++lv) job.t[lv] = t_[lv].p;
+    mlp->set_ray_grad_job(&job);
+    ray_grad_valid_ = true;
+  }
   if (cross_) {
     float* const* g = run_cross(n, o, d, radii, lm, pix, msum, cb_in, user, flags);
     last_n_ = n;
@@ -1386,6 +1443,19 @@ float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* 
     timer.end(kTSample);
   }
   return mlp->publish_cross(flags);
+}
+
+void AcceleratedMipNeRF::set_ray_grad(bool on) {
+  mlp->set_ray_grad(on);
+  ray_grad_valid_ = false;
+}
+
+void AcceleratedMipNeRF::ray_grad(const float** o_grad, const float** d_grad) const {
+  NOF_REQUIRE(o_grad && d_grad, "null argument");
+  NOF_REQUIRE(mlp->ray_grad() && ray_grad_valid_ && last_n_ > 0,
+              "ray gradients are available after a step with nof_mipnerf_set_ray_grad(h, 1)");
+  *o_grad = mlp->ray_o_grad();
+  *d_grad = mlp->ray_d_grad();
 }
 
 void AcceleratedMipNeRF::cross_view(int level, const float** w_grad, const float** t_grad) const {

@@ -172,6 +172,23 @@ class AcceleratedMLP {
                             const float** denc);
   float* const* publish_cross(uint32_t flags) { return gen_publish((flags & NOF_GRAD_PUBLISH) && hook_); }
   const float* enc_pos(int level) const { return gl_[level].ep; }  // the encoding the level's last forward read
+  // Ray gradients (include/nof.h nof_mipnerf_set_ray_grad; any-shape path only, else NOF_ERR_UNSUPPORTED).  on:
+  // allocates dL/dEnc's buffers for every level, dL/d(view PE) and the two outputs; off: nothing is freed.  While
+  // the owner has a job set (the step's rays and each level's t), every level's backward also forms dEnc and
+  // dDir = (the view layer's per-ray deltas) W_view[:, W : W + Vd], and k_ray_grad runs right after it (dEnc
+  // and the per-ray deltas are single buffers, overwritten by the next level): the first level of a job overwrites
+  // the outputs, later ones add.
+  struct RayGradJob {
+    int n = 0;
+    const float *o = nullptr, *d = nullptr, *radius = nullptr;
+    const float* t[NOF_MAX_LEVELS] = {};
+    bool first = true;
+  };
+  void set_ray_grad(bool on);
+  bool ray_grad() const { return ray_grad_; }
+  void set_ray_grad_job(const RayGradJob* job) { rg_job_ = job ? *job : RayGradJob(); }
+  const float* ray_o_grad() const { return rg_o_.p; }
+  const float* ray_d_grad() const { return rg_d_.p; }
 
  private:
   struct Schedule {
@@ -254,6 +271,10 @@ class AcceleratedMLP {
   // its pair is formed), dL/dEnc [M][P] and, with more than two contributing layers, the pairs' partial sums
   bool cross_ = false;
   DevBuf<float> gd2_, gdenc_, gdenc_part_;
+  void denc_alloc(int first_level);  // those three, for levels >= first_level (grown, never shrunk)
+  bool ray_grad_ = false;
+  RayGradJob rg_job_;
+  DevBuf<float> gddir_, rg_o_, rg_d_;  // dL/d(view PE) [rays][Vd]; dL/do, dL/dd [rays][3]
   // non-null: gen_backward launches nothing and gen_wgrad records its split-K slab need here instead (the
   // slab is sized at construction by a dry run of the same call sequence a step makes)
   size_t* wg_need_ = nullptr;
@@ -309,6 +330,9 @@ class AcceleratedMipNeRF {
   void get_rng(uint64_t* seed, uint32_t* step, uint32_t* ray_base) const { *seed = seed_; *step = step_; *ray_base = ray_base_; }
   nof_level_view level_view(int level) const;
   void cross_view(int level, const float** w_grad, const float** t_grad) const;
+  // dL/d origins, dL/d directions of the last step's rays (nof_mipnerf_set_ray_grad / nof_mipnerf_ray_grad)
+  void set_ray_grad(bool on);
+  void ray_grad(const float** o_grad, const float** d_grad) const;
   float loss();
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
@@ -335,6 +359,7 @@ class AcceleratedMipNeRF {
   uint32_t step_ = 0, ray_base_ = 0;
   int last_n_ = 0;
   bool last_fused_ = false;
+  bool ray_grad_valid_ = false;  // a step has run since the option was switched on
   DevBuf<float> o_, d_, radii_, nears_, fars_, lm_, pix_;
   std::vector<DevBuf<float>> t_, w_, C_, dsig_, drgb_, loss_rays_, acc_, dist_;
   // stop_level_grad = 0 (allocated only then): q^l = dL/dw^l [n][S] (levels < L - 1); for levels >= 1 the

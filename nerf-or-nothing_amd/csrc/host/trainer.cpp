@@ -272,6 +272,7 @@ void RayDataset::next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hi
       });
     }
   }
+  last_n_ = n;
   out->n = n;
   out->origins = o_.p; out->directions = d_.p; out->viewdirs = vd_.p; out->radii = r_.p;
   out->nears = nr_.p; out->fars = fr_.p; out->loss_mults = lm_.p; out->pixels = pix_.p; out->record_index = idx_.p;
@@ -279,6 +280,37 @@ void RayDataset::next(int n, uint64_t seed, uint32_t step, uint32_t ray_base, hi
     NOF_HIP(hipMemcpyAsync(host_msum, msum_.p, sizeof(float), hipMemcpyDeviceToHost, st));
     NOF_HIP(hipStreamSynchronize(st));
   }
+}
+
+// ---- camera refinement: pose gradients and pose updates (include/nof.h nof_dataset_pose_grad) -----------------
+void RayDataset::pose_grad(int n, const float* dev_o_grad, const float* dev_d_grad, float* dev_pose_grad,
+                           int accumulate, hipStream_t st) {
+  if (!image_backed())
+    throw Error(NOF_ERR_UNSUPPORTED, "pose_grad needs an image-backed dataset (nof_dataset_from_images)");
+  if (ndc_) throw Error(NOF_ERR_UNSUPPORTED, "pose_grad: the NDC warp (ConvertToNdc) is not differentiated");
+  NOF_REQUIRE(dev_o_grad && dev_d_grad && dev_pose_grad, "null argument");
+  NOF_REQUIRE(last_n_ > 0, "pose_grad before nof_dataset_next");
+  NOF_REQUIRE(n > 0 && n <= last_n_, "n exceeds the last batch");
+  NOF_HIP(hipSetDevice(device_));
+  NOF_HIP(nof::launch_pose_grad(layout_, n, idx_.p, dev_o_grad, dev_d_grad, dev_pose_grad, accumulate, st));
+}
+
+void RayDataset::get_poses(float* host_poses) {
+  if (!image_backed())
+    throw Error(NOF_ERR_UNSUPPORTED, "get_poses needs an image-backed dataset (nof_dataset_from_images)");
+  NOF_REQUIRE(host_poses != nullptr, "null poses");
+  NOF_HIP(hipSetDevice(device_));
+  NOF_HIP(hipDeviceSynchronize());
+  NOF_HIP(hipMemcpy(host_poses, poses_.p, poses_.n * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void RayDataset::set_poses(const float* host_poses) {
+  if (!image_backed())
+    throw Error(NOF_ERR_UNSUPPORTED, "set_poses needs an image-backed dataset (nof_dataset_from_images)");
+  NOF_REQUIRE(host_poses != nullptr, "null poses");
+  NOF_HIP(hipSetDevice(device_));
+  NOF_HIP(hipDeviceSynchronize());  // an earlier gather or view may still read the table
+  NOF_HIP(hipMemcpy(poses_.p, host_poses, poses_.n * sizeof(float), hipMemcpyHostToDevice));
 }
 
 // ---- whole views (the test split) -----------------------------------------------------------------

@@ -62,6 +62,14 @@ class RayDataset {
   // nof_dataset_render_view).  The chunk rays are buffers of their own: next()'s batch stays as it is.
   void render_view(AcceleratedMipNeRF& model, int view, const float* host_pose, int scale, const nof_view_out& out,
                    nof_view_metrics* metrics, uint32_t flags);
+  // Image-backed, ndc = 0 (else NOF_ERR_UNSUPPORTED, before any launch): the gradients [n][3] of the LAST next()
+  // batch's rays summed per view into dev_pose_grad [V][12] (dataset.hip k_pose_grad), on st.
+  void pose_grad(int n, const float* dev_o_grad, const float* dev_d_grad, float* dev_pose_grad, int accumulate,
+                 hipStream_t st);
+  // The pose table (V x 12, host).  set_poses waits for the device's work, then copies: the next gather and
+  // render_view read the new poses.
+  void get_poses(float* host_poses);
+  void set_poses(const float* host_poses);
 
  private:
   void reserve(int n, hipStream_t st);
@@ -96,6 +104,7 @@ class RayDataset {
   std::thread prefetch_;
   std::string prefetch_error_;
   int cap_ = 0;
+  int last_n_ = 0;  // rays of the last next() batch (idx_ holds their record indices)
   DevBuf<float> o_, d_, vd_, r_, nr_, fr_, lm_, pix_, msum_;
   DevBuf<int> idx_;
   // render_view's state: the chunk's rays, the score's per-block partials ([levels][blocks of a scale-0

@@ -128,6 +128,59 @@ hipError_t launch_gather_rays(const float* poses, const float* pyr, const Multis
   return hipGetLastError();
 }
 
+// Pose gradients of an image-backed batch (ndc = 0): ray_at gives o = P[9..11], d_i = sum_c P[3 i + c] cam_c with
+// cam = pixel_dir's (cx, cy, cz) at the ray's own scale, so dL/dP[9 + i] = sum dL/do_i and dL/dP[3 i + c] =
+// sum dL/dd_i cam_c over the view's rays.  One workgroup per view scans the batch's n record indices (O(V n) index
+// reads: nothing next to a step); thread t keeps the view's rays t, t + 256, ... in ray order in 12 accumulators,
+// then a fixed tree.  No atomics: bitwise repeatable.
+constexpr int kPoseGradThreads = 256;
+__global__ __launch_bounds__(kPoseGradThreads) void k_pose_grad(MultiscaleLayout L, int n, const int* __restrict__ idx,
+                                                                const float* __restrict__ og,
+                                                                const float* __restrict__ dg,
+                                                                float* __restrict__ pose_grad, int accumulate) {
+  __shared__ float red[13][kPoseGradThreads];
+  const int v = blockIdx.x, tid = threadIdx.x;
+  float acc[13];
+#pragma unroll
+  for (int k = 0; k < 13; ++k) acc[k] = 0.0f;
+  for (int r = tid; r < n; r += kPoseGradThreads) {
+    const RecordPos p = record_pos(L, (uint32_t)idx[r]);
+    if (p.v != v) continue;
+    const float cam[3] = {((float)p.x - (float)p.w * 0.5f + 0.5f) / p.focal,
+                          -((float)p.y - (float)p.h * 0.5f + 0.5f) / p.focal, -1.0f};  // pixel_dir's
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float gd = dg[3 * r + i];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[3 * i + c] += gd * cam[c];
+      acc[9 + i] += og[3 * r + i];
+    }
+    acc[12] += 1.0f;  // (the view's ray count: an empty view leaves an accumulated row as it is)
+  }
+#pragma unroll
+  for (int k = 0; k < 13; ++k) red[k][tid] = acc[k];
+  __syncthreads();
+  for (int o = kPoseGradThreads / 2; o > 0; o >>= 1) {
+    if (tid < o)
+#pragma unroll
+      for (int k = 0; k < 13; ++k) red[k][tid] += red[k][tid + o];
+    __syncthreads();
+  }
+  if (tid < 12) {
+    float* dst = pose_grad + 12 * (size_t)v + tid;
+    if (!accumulate) *dst = red[tid][0];
+    else if (red[12][0] > 0.0f) *dst = *dst + red[tid][0];
+  }
+}
+
+hipError_t launch_pose_grad(const MultiscaleLayout& L, int n, const int* idx, const float* o_grad, const float* d_grad,
+                            float* pose_grad, int accumulate, hipStream_t st) {
+  if (L.num_views <= 0 || n < 0 || !idx || !o_grad || !d_grad || !pose_grad) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pose_grad, dim3(L.num_views), dim3(kPoseGradThreads), 0, st, L, n, idx, o_grad, d_grad,
+                     pose_grad, accumulate);
+  return hipGetLastError();
+}
+
 // fails kChkSelfTest on purpose: proves a checked build's plumbing (nof_device_checks_selftest)
 __global__ void k_check_selftest(int zero) { NOF_DCHECK(zero != 0, kChkSelfTest); }
 hipError_t launch_check_selftest(hipStream_t st) {

@@ -129,6 +129,18 @@ struct SamplePdfGradArgs {
 };
 hipError_t launch_sample_pdf_grad(const SamplePdfGradArgs& a, hipStream_t st);
 
+// ---- raygrad.hip: one level's share of dL/d(origin), dL/d(direction) per ray (nof_mipnerf_set_ray_grad) ------
+// o_grad / d_grad [n][3] (accumulate: added to, else overwritten) from enc / denc [n S][P] (as EncodeGradArgs), the
+// level's sigma / dsigma [n S] (the integrator's |d|) and, ddir != null, the view encoding enc_dir / ddir [n][Vd]
+// (Vd = 3 + 6 deg_view, dir_feature's order).  S a multiple of 32, at most 512.
+struct RayGradArgs {
+  int n, S, P, min_deg, cylinder, Vd, accumulate;
+  const float *t, *o, *d, *radius, *enc, *denc, *sigma, *dsigma;
+  const float *enc_dir, *ddir;
+  float *o_grad, *d_grad;
+};
+hipError_t launch_ray_grad(const RayGradArgs& a, hipStream_t st);
+
 // ---- mlp_fwd.hip / mlp_bwd.hip -----------------------------------------------------------------
 struct FwdArgs {
   int M, S, encoded;
@@ -361,6 +373,11 @@ hipError_t launch_gather_rays(const float* poses, const float* pyr, const Multis
                               int ndc, int n, uint64_t seed, uint32_t step, uint32_t ray_base, float* o, float* d,
                               float* vd, float* radius, float* nears, float* fars, float* lm, float* pix, int* idx_out,
                               float* lm_sum, hipStream_t st);
+// dataset.hip: the rays' gradients o_grad / d_grad [n][3] of a batch of an image-backed scene (ndc = 0) summed per
+// view into pose_grad [V][12] (rotation row-major, then translation: d = R cam(x, y, scale), o = t); idx: the
+// batch's record indices.  A view without a ray: 0, or unchanged when accumulating.
+hipError_t launch_pose_grad(const MultiscaleLayout& L, int n, const int* idx, const float* o_grad, const float* d_grad,
+                            float* pose_grad, int accumulate, hipStream_t st);
 
 // ---- view.hip: a whole view of an image-backed scene, chunk by chunk (include/nof.h nof_dataset_render_view) ----
 // The rays of pixels [p0, p0 + n) of a w x h view (one scale's row of the MultiscaleLayout), row-major, into a

@@ -130,6 +130,8 @@ SIGNATURES = {
     "nof_mipnerf_get_rng": [P, C.POINTER(U64), C.POINTER(U32), C.POINTER(U32)],
     "nof_mipnerf_level_view": [P, I32, C.POINTER(nof_level_view)],
     "nof_mipnerf_cross_view": [P, I32, C.POINTER(P), C.POINTER(P)],
+    "nof_mipnerf_set_ray_grad": [P, I32],
+    "nof_mipnerf_ray_grad": [P, C.POINTER(P), C.POINTER(P)],
     "nof_mipnerf_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],
@@ -151,6 +153,9 @@ SIGNATURES = {
     "nof_dataset_materialize": [P, P, P],
     "nof_dataset_scene_info": [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)],
     "nof_dataset_render_view": [P, P, I32, P, I32, U32, C.POINTER(nof_view_out), C.POINTER(nof_view_metrics)],
+    "nof_dataset_pose_grad": [P, I32, P, P, P, I32, P],
+    "nof_dataset_get_poses": [P, P],
+    "nof_dataset_set_poses": [P, P],
     "nof_recenter_poses": [P, I32],
     "nof_dp_unique_id": [P],
     "nof_dp_init_rank": [P, I32, I32, I32, C.POINTER(P)],
@@ -218,6 +223,7 @@ SIGNATURES = {
     "nof_kernel_render_grad_ex": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P],
     "nof_kernel_sample_pdf_grad": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P, P],
     "nof_kernel_encode_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P],
+    "nof_kernel_ray_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P],
     "nof_kernel_adam": [C.c_int64, P, P, P, P, F, I32, P],
     "nof_kernel_gemm_h": [C.POINTER(nof_gemm_args), P],
 }

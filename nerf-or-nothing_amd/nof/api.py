@@ -343,6 +343,17 @@ class AcceleratedMipNeRF:
         return {"w_grad": to_numpy(q.value, (v.n, v.samples)) if q.value else None,
                 "t_grad": to_numpy(dt.value, (v.n, v.samples + 1)) if dt.value else None}
 
+    def set_ray_grad(self, on: bool = True) -> None:
+        """Every later step also leaves dL/d origins, dL/d directions of its rays (include/nof.h
+        nof_mipnerf_set_ray_grad; any-shape path only: a fused 8x256 model raises NofError(NOF_ERR_UNSUPPORTED))."""
+        call("nof_mipnerf_set_ray_grad", self._h, int(bool(on)))
+
+    def ray_grad(self):
+        """The last step's (dL/do, dL/dd) as borrowed device pointers, each [n, 3] (to_numpy / device_tensor)."""
+        o, d = C.c_void_p(), C.c_void_p()
+        call("nof_mipnerf_ray_grad", self._h, C.byref(o), C.byref(d))
+        return o.value, d.value
+
     def loss(self) -> float:
         out = C.c_float()
         call("nof_mipnerf_loss", self._h, C.byref(out))
@@ -628,6 +639,35 @@ class RayDataset:
         if score:
             res.update(mse=list(m.mse[:L_]), psnr=list(m.psnr[:L_]), ssim=m.ssim if ssim else None)
         return res
+
+    def pose_grad(self, o_grad, d_grad, n: int, out=None, accumulate: bool = False, stream=None):
+        """Camera refinement (include/nof.h nof_dataset_pose_grad): the gradients [n, 3] of the LAST next() batch's
+        rays (AcceleratedMipNeRF.ray_grad()) summed per view -> torch device tensor [V, 12] (rotation row-major,
+        then translation), enqueued on `stream`; out: a tensor to write (accumulate: to add to).  An NDC scene or a
+        record dataset raises NofError(NOF_ERR_UNSUPPORTED)."""
+        import torch
+
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs the tensor to add to (out)")
+            out = torch.zeros((self.scene_info()["num_views"], 12), dtype=torch.float32,
+                              device=torch.device("cuda", self._device))
+        call("nof_dataset_pose_grad", self._h, int(n), _ptr(o_grad), _ptr(d_grad), out.data_ptr(), int(accumulate),
+             stream)
+        return out
+
+    def poses(self) -> np.ndarray:
+        """The image-backed dataset's pose table [V, 12] (host copy)."""
+        P = np.empty((self.scene_info()["num_views"], 12), np.float32)
+        call("nof_dataset_get_poses", self._h, P.ctypes.data)
+        return P
+
+    def set_poses(self, P) -> None:
+        """Replace the pose table ([V, 12]: rotation row-major, then translation): the next batch and render_view use it."""
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        if P.size != 12 * self.scene_info()["num_views"]:
+            raise ValueError("set_poses takes every view's pose: [V, 12]")
+        call("nof_dataset_set_poses", self._h, P.ctypes.data)
 
     def close(self):
         if getattr(self, "_h", None):

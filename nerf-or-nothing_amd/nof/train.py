@@ -7,6 +7,8 @@ never implements.
     python -m nof.train --scene scene.npz --num-scales 4        (poses + images, rays made per batch)
     python -m nof.train --scene scene.npz --holdout 8 --eval-every 10000 [--eval-dir renders]
                                                                 (every 8th view held out, rendered and scored)
+    python -m nof.train --scene scene.npz --refine-poses 1e-3 --precision f16p
+                                                                (the scene's poses refined jointly with the field)
 
 One step = dataset batch (device gather) -> AcceleratedMipNeRF.get_gradient_device (fused loss
 gradient) -> [all-reduce of the gradient arena when torch.distributed is initialised] ->
@@ -22,7 +24,7 @@ import time
 import numpy as np
 
 from . import api
-from ._lib import PRECISION_NAMES, default_config
+from ._lib import PRECISION_NAMES, NofError, default_config
 
 
 class Trainer:
@@ -30,7 +32,7 @@ class Trainer:
                  stream=None, print_every: int = 100, save_every: int = 0, ckpt_dir: str | None = None,
                  sync_check_every: int = 0, lr_init=5e-4, lr_final=5e-6, max_steps=1000000, lr_delay_steps=2500, lr_delay_mult=0.01,
                  grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
-                 stats: bool = False, **config):
+                 stats: bool = False, refine_poses: float = 0.0, **config):
         import torch.distributed as dist
 
         self.dist = dist if dist.is_available() and dist.is_initialized() else None
@@ -65,6 +67,12 @@ class Trainer:
             from .dp import BucketedAllReduce
 
             self._allreduce = BucketedAllReduce(self.model, f"cuda:{device}")
+        # camera refinement: refused here, before training, with the library's message, by a model
+        # without ray gradients (a fused 8x256 precision) and by a dataset without pose gradients (NDC, records)
+        self.refiner = None
+        if refine_poses:
+            self.model.set_ray_grad(True)
+            self.refiner = PoseRefiner(dataset, batch_size, refine_poses, seed, device, stream)
 
     # --- checkpoints -----------------------------------------------------------------------------
     def save(self, path):
@@ -90,6 +98,8 @@ class Trainer:
         grads = self.model.get_gradient_device(self.n, p["o"], p["d"], p["radius"], p["near"], p["far"],
                                                p["lossmult"], p["pix"], msum)
         self.adam.step(self.params, grads, api.learning_rate_decay(step, **self.lr))
+        if self.refiner is not None:  # this batch's pose gradient; the corrected poses make the next batch's rays
+            self.refiner.step(self.model, self.n, self.dist)
         self.step_idx = step
         if self.print_every and step % self.print_every == 0:
             bad = self.model.numeric_status(clear=True)
@@ -113,6 +123,16 @@ class Trainer:
         if self.save_every and self.ckpt_dir and step % self.save_every == 0 and self.rank == 0:
             os.makedirs(self.ckpt_dir, exist_ok=True)
             self.save(os.path.join(self.ckpt_dir, f"ckpt_{step:08d}.nof"))
+            self.save_poses()
+
+    def save_poses(self):
+        """--refine-poses: the refined pose table [V, 12] as poses_refined.npy next to the checkpoints (a checkpoint
+        does not hold poses)"""
+        if self.refiner is None or self.rank != 0:
+            return
+        d = self.ckpt_dir or "."
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "poses_refined.npy"), self.refiner.poses())
 
     def check_sync(self):
         """SURVEY §8e's periodic assertion: every rank's parameters are bitwise identical (a rank that
@@ -168,6 +188,56 @@ class Trainer:
                             psnr_coarse=float(np.mean([x["psnr_coarse"] for x in views])),
                             ssim=float(np.mean([x["ssim"] for x in views])) if ssim else None))
         return out
+
+
+class PoseRefiner:
+    """Joint pose refinement: per view delta_v = (omega_v, tau_v) in R^6 (a small torch tensor, zero at the start),
+    pose_v = (exp(hat omega_v) R0_v, t0_v + tau_v), so every rotation stays orthonormal by construction.  The
+    library's pose gradient [V, 12] (RayDataset.pose_grad of AcceleratedMipNeRF.ray_grad) is pushed through that
+    map by torch autograd with the surrogate (pose * grad.detach()).sum(), delta is stepped by torch.optim.Adam, and
+    the new table goes back with RayDataset.set_poses before the next batch is drawn."""
+
+    def __init__(self, dataset: api.RayDataset, n: int, lr: float, seed: int, device: int, stream=None):
+        import torch
+
+        self.ds, self.stream = dataset, stream
+        self.dev = torch.device("cuda", device)
+        # a batch and a zero gradient through the library once: an NDC scene or a record dataset is refused now
+        dataset.next(n, seed, 0, 0, stream, with_sum=False)
+        zero = torch.zeros((n, 3), dtype=torch.float32, device=self.dev)
+        self.grad = dataset.pose_grad(zero, zero, n, stream=stream)
+        P0 = torch.from_numpy(dataset.poses().astype(np.float64))
+        self.R0, self.t0 = P0[:, :9].reshape(-1, 3, 3), P0[:, 9:]
+        self.delta = torch.zeros((P0.shape[0], 6), dtype=torch.float64, requires_grad=True)
+        self.opt = torch.optim.Adam([self.delta], lr=lr)
+
+    def _poses(self):
+        import torch
+
+        w = self.delta[:, :3]
+        z = torch.zeros_like(w[:, 0])
+        hat = torch.stack([torch.stack([z, -w[:, 2], w[:, 1]], -1), torch.stack([w[:, 2], z, -w[:, 0]], -1),
+                           torch.stack([-w[:, 1], w[:, 0], z], -1)], -2)
+        R = torch.linalg.matrix_exp(hat) @ self.R0
+        return torch.cat([R.reshape(-1, 9), self.t0 + self.delta[:, 3:]], 1)
+
+    def poses(self) -> np.ndarray:
+        import torch
+
+        with torch.no_grad():
+            return self._poses().numpy().astype(np.float32)
+
+    def step(self, model: api.AcceleratedMipNeRF, n: int, dist=None):
+        og, dg = model.ray_grad()
+        self.ds.pose_grad(og, dg, n, out=self.grad, stream=self.stream)
+        api.call("nof_stream_sync", self.stream)
+        if dist is not None:  # every rank's shard of the batch
+            dist.all_reduce(self.grad)
+        g = self.grad.cpu().double()
+        self.opt.zero_grad()
+        (self._poses() * g).sum().backward()
+        self.opt.step()
+        self.ds.set_poses(self.poses())
 
 
 def holdout_views(num_views: int, holdout: int, split: str = "train") -> list[int]:
@@ -254,6 +324,14 @@ def parse_args(argv=None):
     ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="weight_decay_mult of the loss term sum p^2 / P")
     ap.add_argument("--stats", action="store_true", help="print the gradient statistics with the loss")
+    # LearningRateDecay (Program.cs:27-33): the schedule's start and its warm-up (the defaults are the reference's)
+    ap.add_argument("--lr-init", type=float, default=5e-4)
+    ap.add_argument("--lr-delay-steps", type=int, default=2500, help="0: no warm-up")
+    ap.add_argument("--refine-poses", type=float, default=0.0, metavar="LR",
+                    help="--scene (not NDC): refine the poses jointly with the field, Adam with this learning rate on a "
+                         "per-view (rotation vector, translation); writes poses_refined.npy into --ckpt-dir (default: "
+                         "the working directory).  Needs the any-shape path: any other network than 8x256 in f32 or "
+                         "f16p; for the reference network --precision f16p, or f32 with --no-stop-level-grad")
     # the test split (Config.LlffHold / GcEvery, TrainState.cs:53,63): held-out views rendered and scored on the device
     ap.add_argument("--holdout", type=int, default=0, metavar="N",
                     help="--scene: hold out every N-th view (i %% N == 0) as the test split; evaluated at the end")
@@ -262,6 +340,10 @@ def parse_args(argv=None):
     ap.add_argument("--eval-dir", metavar="DIR",
                     help="with --holdout: write each rendered test view's rgb, distance and acc as .npy files")
     a = ap.parse_args(argv)
+    if a.refine_poses < 0:
+        ap.error("--refine-poses takes a learning rate > 0")
+    if a.refine_poses and not a.scene:
+        ap.error("--refine-poses needs --scene: only a scene of poses and images has poses to refine")
     if a.holdout < 0 or a.holdout == 1:
         ap.error("--holdout must be 0 (off) or at least 2: every N-th view is held out, so 1 leaves nothing to train on")
     if a.eval_every < 0:
@@ -289,11 +371,16 @@ def main(argv=None):
         ds = api.RayDataset(a.records, device=a.device)
     else:
         ds = api.RayDataset(records=synth.pack_records(synth.blender_rays(a.synthetic, seed=1)), device=a.device)
-    tr = Trainer(ds, batch_size=a.batch, device=a.device, print_every=a.print_every, save_every=a.save_every,
-                 ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
-                 grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
-                 stats=a.stats,
-                 precision=PRECISION_NAMES[a.precision], **net)
+    try:
+        tr = Trainer(ds, batch_size=a.batch, device=a.device, print_every=a.print_every, save_every=a.save_every,
+                     ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
+                     grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
+                     stats=a.stats, refine_poses=a.refine_poses, lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
+                     precision=PRECISION_NAMES[a.precision], **net)
+    except NofError as e:
+        if a.refine_poses and e.status == 5:  # NOF_ERR_UNSUPPORTED: the library says what --refine-poses needs
+            raise SystemExit(f"--refine-poses: {e}")
+        raise
     if a.resume:
         tr.resume(a.resume)
     test = None
@@ -320,6 +407,7 @@ def main(argv=None):
     import torch
 
     torch.cuda.synchronize()
+    tr.save_poses()
     dt = time.perf_counter() - t0
     print(f"{a.steps} steps in {dt:.3f} s: {a.steps * a.batch / dt:.1f} rays/s", flush=True)
 
