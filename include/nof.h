@@ -83,9 +83,23 @@ typedef struct nof_config {
                                              network is routed there) or NOF_PRECISION_F16_PRODUCTS; the fused
                                              8x256 modes produce no input gradient: NOF_ERR_UNSUPPORTED.  The
                                              forward is unchanged by the option; num_levels == 1: a no-op */
+  float distortion_loss_mult;             /* lambda_d >= 0, default 0 = off (no counterpart in the reference): the
+                                             distortion loss of mip-NeRF 360 on the LAST level's weights, added to
+                                             the objective as lambda_d sum_r mu_r L_r / sum mu with
+                                               L_r = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+                                             over the midpoints m and widths delta of the normalised distance
+                                             s(t) = (t - near) / (far - near), or with lindisp = 1
+                                             (1/near - 1/t) / (1/near - 1/far).  Its gradient joins the integrator
+                                             adjoint: every precision mode and network; with
+                                             stop_level_grad = 0 its dL/dt also trains the coarser levels.  A ray
+                                             whose far - near (lindisp: near, 1/near - 1/far) is not a positive
+                                             finite number contributes nothing.  Negative or non-finite:
+                                             NOF_ERR_INVALID_ARG.  nof_mipnerf_loss stays the photometric loss;
+                                             the term is read with nof_mipnerf_distortion_loss */
 } nof_config;
 /* The struct grows at its end only (grad_buckets, then lindisp / ray_shape, then density_bias / rgb_padding, then
- * stop_level_grad): a binding
+ * stop_level_grad, then distortion_loss_mult, which fills the 4 bytes of tail padding the 8-byte aligned struct had:
+ * sizeof(nof_config) did not change with it, and an older binding's zeroed struct reads as 0 = off): a binding
  * compiled against an older header passes a shorter struct.  nof_config_size() is sizeof(nof_config) of
  * this library; a binding checks it against its own struct size before passing one. */
 size_t nof_config_size(void);
@@ -235,6 +249,10 @@ nof_status nof_mipnerf_set_ray_grad(nof_mipnerf* h, int32_t enable);
 nof_status nof_mipnerf_ray_grad(nof_mipnerf* h, const float** dev_o_grad, const float** dev_d_grad);
 /* sum over rays and levels of lambda_l * m_r |C - p|^2 / sum m (fused path only; synchronises) */
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out);
+/* nof_config.distortion_loss_mult's term of the last gradient step, lambda_d sum_r mu_r L_r / sum mu (either
+ * gradient entry; the per-ray terms summed on the host in ray order; synchronises).  0 with the option off;
+ * NOF_ERR_INVALID_ARG before a step. */
+nof_status nof_mipnerf_distortion_loss(nof_mipnerf* h, float* out);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
  * stated limit: an overflow surfaces here instead of silently): NOF_NUMERIC_FORWARD = a training
  * forward produced a non-finite composite colour; NOF_NUMERIC_DELTA = the f16x2 delta scaling saw a
@@ -648,6 +666,19 @@ nof_status nof_kernel_render_grad_ex(int32_t n, int32_t samples, const float* de
                                      const float* dev_g, const float* pixels, const float* loss_mults,
                                      float loss_mult_sum, float lambda, float* density_grad, float* rgb_grad,
                                      const float* dev_w_grad, float* dev_t_grad, void* stream);
+/* nof_kernel_render_grad_ex with the distortion loss (nof_config.distortion_loss_mult) of this level: nears / fars
+ * [n] and lindisp give the normalised distance; dist_mult lossmult[r] / loss_mult_sum L_r is added to the objective
+ * (loss_mults and loss_mult_sum are needed for it also when dev_g supplies dL/dC); dev_dist_rays ([n] or NULL)
+ * receives that per-ray term.  dev_w_grad and dev_t_grad both NULL: k_render_bwd<., true>, else
+ * k_render_bwd_x<., true> (the term's dL/dt added to dev_t_grad).  dist_mult = 0: the kernels without the term, so
+ * nof_kernel_render_grad_ex bit for bit (dev_dist_rays zeroed). */
+nof_status nof_kernel_render_grad_dist(int32_t n, int32_t samples, const float* density, const float* rgb,
+                                       const float* t, const float* dirs, int32_t white_bkgd, const float* comp_rgb,
+                                       const float* dev_g, const float* pixels, const float* loss_mults,
+                                       float loss_mult_sum, float lambda, float* density_grad, float* rgb_grad,
+                                       const float* dev_w_grad, float* dev_t_grad, const float* nears,
+                                       const float* fars, int32_t lindisp, float dist_mult, float* dev_dist_rays,
+                                       void* stream);
 /* The adjoint of nof_kernel_sample_pdf (the same sampling arguments; the forward's bin index, clamps, cdf
  * saturation, pad branch and blur-pool max picks are recomputed and held): dev_t_out_grad [n][S_out + 1] ->
  * dev_w_grad [n][S_in] and dev_t_in_grad [n][S_in + 1] (or NULL: not wanted), both overwritten. */

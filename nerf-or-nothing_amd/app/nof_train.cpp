@@ -67,6 +67,7 @@ struct Args {
   bool lindisp = false, cylinder = false;
   float density_bias = -1.0f, rgb_padding = 0.001f;
   bool no_stop_level_grad = false;  // MipNerfModel.StopLevelGrad = false (MipNerfModel.cs:13)
+  float distortion_loss_mult = 0.0f;  // nof_config.distortion_loss_mult (0 = off)
   // Config (TrainState.cs:54-58)
   float lr_init = 5e-4f, lr_final = 5e-6f, lr_delay_mult = 0.01f;
   int max_steps = 1000000, lr_delay_steps = 2500;
@@ -85,7 +86,7 @@ struct Args {
                "                 [--samples S0,S1[,...]]  (e.g. BASELINE configs[0]: --net-depth 4 --net-width 128 "
                "--samples 64,64)\n"
                "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n"
-               "                 [--no-stop-level-grad]\n"
+               "                 [--no-stop-level-grad] [--distortion-loss-mult X]\n"
                "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n");
   std::exit(code);
 }
@@ -119,6 +120,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--density-bias") a.density_bias = std::strtof(val(), nullptr);
     else if (k == "--rgb-padding") a.rgb_padding = std::strtof(val(), nullptr);
     else if (k == "--no-stop-level-grad") a.no_stop_level_grad = true;
+    else if (k == "--distortion-loss-mult") a.distortion_loss_mult = std::strtof(val(), nullptr);
     else if (k == "--grad-max-norm") a.grad_max_norm = std::strtof(val(), nullptr);
     else if (k == "--grad-max-val") a.grad_max_val = std::strtof(val(), nullptr);
     else if (k == "--weight-decay") a.weight_decay = std::strtof(val(), nullptr);
@@ -261,6 +263,7 @@ int main(int argc, char** argv) {
     R.cfg.density_bias = a.density_bias;
     R.cfg.rgb_padding = a.rgb_padding;
     R.cfg.stop_level_grad = a.no_stop_level_grad ? 0 : 1;
+    R.cfg.distortion_loss_mult = a.distortion_loss_mult;
     if (a.net_depth) R.cfg.net_depth = a.net_depth;  // other shapes: the any-shape fp32 path
     if (a.net_width) R.cfg.net_width = a.net_width;
     if (a.net_depth_condition) R.cfg.net_depth_condition = a.net_depth_condition;
@@ -377,6 +380,16 @@ int main(int argc, char** argv) {
         den += m;
       }
       std::printf("Step %d/%d, Loss: %.9g", step, a.max_steps, G == 1 ? (double)loss1 : num / den);
+      if (a.distortion_loss_mult > 0.0f) {  // each replica's term is over the global sum mu: the terms add up
+        double dist = 0.0;                  // (of every replica's last micro-batch)
+        for (Replica& R : rs) {
+          float x = 0.0f;
+          CHECK(nof_set_device(R.device));
+          CHECK(nof_mipnerf_distortion_loss(R.model, &x));
+          dist += (double)x;
+        }
+        std::printf(", Distortion: %.9g", dist);
+      }
       if (with_stats) {  // of the all-reduced gradient: the same record on every replica
         nof_step_stats st;
         CHECK(nof_adam_stats(rs[0].adam, &st));

@@ -102,6 +102,7 @@ void nof_config_default(nof_config* c) {
   c->density_bias = -1.0f;  // MNcs:20
   c->rgb_padding = 0.001f;  // MNcs:22
   c->stop_level_grad = 1;   // MNcs:13
+  c->distortion_loss_mult = 0.0f;  // (no counterpart in the reference: off)
 }
 
 size_t nof_config_size(void) { return sizeof(nof_config); }
@@ -240,6 +241,9 @@ nof_status nof_mipnerf_ray_grad(nof_mipnerf* h, const float** dev_o_grad, const 
 }
 nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out) {
   return guard([&] { ARG(h && out); DEV(h); *out = h->impl->loss(); });
+}
+nof_status nof_mipnerf_distortion_loss(nof_mipnerf* h, float* out) {
+  return guard([&] { ARG(h && out); DEV(h); *out = h->impl->distortion_loss(); });
 }
 nof_status nof_mipnerf_render_device(nof_mipnerf* h, int32_t n, const float* o, const float* d, const float* radii,
                                      const float* nears, const float* fars, int32_t randomized, int32_t white_bkgd,
@@ -754,6 +758,35 @@ nof_status nof_kernel_render_grad_ex(int32_t n, int32_t S, const float* sigma, c
     a.n = n; a.S = S; a.white = white; a.d = d; a.pix = pix; a.lossmult = lm; a.msum = msum;
     a.sigma = sigma; a.rgb = rgb; a.t = t; a.C = C; a.g_ext = g; a.lam = lam; a.dsigma = dsigma; a.drgb = drgb;
     a.q = w_grad; a.t_grad = t_grad;
+    NOF_HIP(nof::launch_render_bwd_x(a, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_render_grad_dist(int32_t n, int32_t S, const float* sigma, const float* rgb, const float* t,
+                                       const float* d, int32_t white, const float* C, const float* g, const float* pix,
+                                       const float* lm, float msum, float lam, float* dsigma, float* drgb,
+                                       const float* w_grad, float* t_grad, const float* nears, const float* fars,
+                                       int32_t lindisp, float dist_mult, float* dist_rays, void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && sigma && rgb && t && d && C && dsigma && drgb);
+    ARG(g || (pix && lm && msum > 0.0f));
+    ARG(nears && fars && (lindisp == 0 || lindisp == 1) && std::isfinite(dist_mult) && dist_mult >= 0.0f);
+    ARG(dist_mult == 0.0f || (lm && msum > 0.0f));
+    if (dist_mult == 0.0f && dist_rays) NOF_HIP(hipMemsetAsync(dist_rays, 0, (size_t)n * sizeof(float), (hipStream_t)stream));
+    if (!w_grad && !t_grad) {  // k_render_bwd<., true> (dist_mult = 0: <., false>, as nof_kernel_render_grad)
+      nof::RenderBwdArgs a{};
+      a.n = n; a.S = S; a.d = d; a.white = white; a.pix = pix; a.lossmult = lm; a.msum = msum;
+      a.nears = nears; a.fars = fars; a.lindisp = lindisp;
+      nof::RenderBwdLevel& L = a.lv[0];
+      L.sigma = sigma; L.rgb = rgb; L.t = t; L.C = C; L.g_ext = g; L.lam = lam; L.dsigma = dsigma; L.drgb = drgb;
+      L.dist_mult = dist_mult; L.dist_rays = dist_rays;
+      NOF_HIP(nof::launch_render_bwd(a, 1, (hipStream_t)stream));
+      return;
+    }
+    nof::RenderBwdXArgs a{};  // k_render_bwd_x<., true> (dist_mult = 0: <., false>)
+    a.n = n; a.S = S; a.white = white; a.d = d; a.pix = pix; a.lossmult = lm; a.msum = msum;
+    a.sigma = sigma; a.rgb = rgb; a.t = t; a.C = C; a.g_ext = g; a.lam = lam; a.dsigma = dsigma; a.drgb = drgb;
+    a.q = w_grad; a.t_grad = t_grad;
+    a.dist_mult = dist_mult; a.dist_rays = dist_rays; a.nears = nears; a.fars = fars; a.lindisp = lindisp;
     NOF_HIP(nof::launch_render_bwd_x(a, (hipStream_t)stream));
   });
 }

@@ -124,6 +124,8 @@ static void check_cfg(const nof_config& c) {
                   c.rgb_padding < 0.5f,
               "density_bias must be finite, rgb_padding in [0, 0.5)");
   NOF_REQUIRE(c.stop_level_grad == 0 || c.stop_level_grad == 1, "stop_level_grad must be 0 or 1");
+  NOF_REQUIRE(std::isfinite(c.distortion_loss_mult) && c.distortion_loss_mult >= 0.0f,
+              "distortion_loss_mult must be finite and >= 0");
   if (c.stop_level_grad == 0 && c.precision != NOF_PRECISION_F32 && c.precision != NOF_PRECISION_F16_PRODUCTS)
     throw Error(NOF_ERR_UNSUPPORTED,
                 "stop_level_grad = 0 needs the gradient with respect to the MLP's encoded input, which the fused "
@@ -1238,6 +1240,7 @@ AcceleratedMipNeRF::AcceleratedMipNeRF(const nof_config& cfg) : mlp(nullptr), cf
     t_[l].alloc(N * (S + 1)); w_[l].alloc(N * S); C_[l].alloc(3 * N); acc_[l].alloc(N); dist_[l].alloc(N);
     dsig_[l].alloc(N * S); drgb_[l].alloc(3 * N * S); loss_rays_[l].alloc(N);
   }
+  dist_rays_.alloc(N);
   cross_ = mlp->cross();
   if (cross_) {
     q_.resize(L); dtr_.resize(L); dtb_.resize(L); dt_.resize(L);
@@ -1336,7 +1339,8 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     ray_grad_valid_ = true;
   }
   if (cross_) {
-    float* const* g = run_cross(n, o, d, radii, lm, pix, msum, cb_in, user, flags);
+    float* const* g = run_cross(n, o, d, radii, nears, fars, lm, pix, msum, cb_in, user, flags);
+    dist_valid_ = true;
     last_n_ = n;
     last_fused_ = cb_in == nullptr;
     ++step_;
@@ -1350,6 +1354,8 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     nof::RenderBwdArgs ra{};
     ra.n = n; ra.d = d; ra.white = cfg_.white_bkgd; ra.pix = pix; ra.lossmult = lm; ra.msum = msum;
     ra.nonfinite = mlp->numeric_flags();
+    const float dmult = cfg_.distortion_loss_mult;  // (0: the launches and instantiations without the term)
+    if (dmult > 0.0f) { ra.nears = nears; ra.fars = fars; ra.lindisp = cfg_.lindisp; }
     int nb = 0;
     auto flush = [&]() {
       if (!nb) return;
@@ -1372,6 +1378,8 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
       R.lam = lv < L - 1 ? cfg_.coarse_loss_mult : 1.0f;
       R.dsigma = dsig_[lv].p; R.drgb = drgb_[lv].p; R.loss_rays = cb ? nullptr : loss_rays_[lv].p;
       R.amax = mlp->claim_delta_amax(lv);
+      R.dist_mult = lv == L - 1 ? dmult : 0.0f;
+      R.dist_rays = lv == L - 1 && dmult > 0.0f ? dist_rays_.p : nullptr;
       if (lv == L - 1 && !cb) {  // its integrator forward first, in its own blocks (k_render_bwd fwd_last)
         ra.fwd_last = 1; ra.fwd_C = C_[lv].p; ra.fwd_w = w_[lv].p;
       }
@@ -1388,6 +1396,7 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     for (int lv = 0; lv < L; ++lv) { cg[lv] = drgb_[lv].p; dg[lv] = dsig_[lv].p; }
     grads = mlp->get_gradient_levels(cg.data(), dg.data(), flags);
   }
+  dist_valid_ = true;
   last_n_ = n;
   last_fused_ = cb == nullptr;
   ++step_;
@@ -1399,8 +1408,8 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
 // (+ dEnc for l >= 1); the encoding adjoint, which also forms dt^l = (dt_render + dt_enc) + dt_bins; the
 // resampler adjoint dt^l -> q^{l-1} and, for l - 1 >= 1, dt_bins^{l-1}.
 float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* d, const float* radii,
-                                            const float* lm, const float* pix, float msum, nof_output_grad_fn cb,
-                                            void* user, uint32_t flags) {
+                                            const float* nears, const float* fars, const float* lm, const float* pix,
+                                            float msum, nof_output_grad_fn cb, void* user, uint32_t flags) {
   const int L = cfg_.num_levels;
   std::vector<const float*> g(L, nullptr);
   if (cb)  // every callback first, in order 0..L-1 (MNcpp:125-127)
@@ -1419,6 +1428,10 @@ float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* 
     ra.dsigma = dsig_[lv].p; ra.drgb = drgb_[lv].p; ra.loss_rays = cb ? nullptr : loss_rays_[lv].p;
     ra.q = lv + 1 < L ? q_[lv].p : nullptr;
     ra.t_grad = lv >= 1 ? dtr_[lv].p : nullptr;
+    if (lv == L - 1 && cfg_.distortion_loss_mult > 0.0f) {  // the distortion loss: dL/dw into e_k, dL/dt into dtr_
+      ra.dist_mult = cfg_.distortion_loss_mult; ra.dist_rays = dist_rays_.p;
+      ra.nears = nears; ra.fars = fars; ra.lindisp = cfg_.lindisp;
+    }
     timer.begin(kTRenderBwd);
     NOF_HIP(nof::launch_render_bwd_x(ra, st_));
     timer.end(kTRenderBwd);
@@ -1490,6 +1503,7 @@ void AcceleratedMipNeRF::Render(int n, const float* o, const float* d, const flo
   out->num_levels = L;
   last_n_ = n;
   last_fused_ = false;  // no loss for a render
+  dist_valid_ = false;
 }
 
 nof_level_view AcceleratedMipNeRF::level_view(int level) const {
@@ -1512,6 +1526,17 @@ float AcceleratedMipNeRF::loss() {
     NOF_HIP(hipStreamSynchronize(st_));
     for (float x : h) s += x;
   }
+  return (float)s;
+}
+
+float AcceleratedMipNeRF::distortion_loss() {
+  if (!(cfg_.distortion_loss_mult > 0.0f)) return 0.0f;
+  NOF_REQUIRE(dist_valid_ && last_n_ > 0, "the distortion loss is available after a gradient step");
+  std::vector<float> h(last_n_);
+  NOF_HIP(hipMemcpyAsync(h.data(), dist_rays_.p, last_n_ * sizeof(float), hipMemcpyDeviceToHost, st_));
+  NOF_HIP(hipStreamSynchronize(st_));
+  double s = 0.0;
+  for (float x : h) s += x;  // (ray order, as loss())
   return (float)s;
 }
 

@@ -334,6 +334,9 @@ class AcceleratedMipNeRF {
   void set_ray_grad(bool on);
   void ray_grad(const float** o_grad, const float** d_grad) const;
   float loss();
+  // nof_config.distortion_loss_mult's term of the last gradient step, lambda_d sum_r mu_r L_r / sum mu (0 with the
+  // option off; synchronises)
+  float distortion_loss();
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
   // per level comp_rgb [n][3], distance [n], acc [n] (device, borrowed until the next call).
@@ -360,14 +363,17 @@ class AcceleratedMipNeRF {
   int last_n_ = 0;
   bool last_fused_ = false;
   bool ray_grad_valid_ = false;  // a step has run since the option was switched on
+  bool dist_valid_ = false;      // the last call was a gradient step (dist_rays_ holds its rays' terms)
+  DevBuf<float> dist_rays_;      // [max_rays]: c_r L_r of the last level (distortion_loss_mult > 0)
   DevBuf<float> o_, d_, radii_, nears_, fars_, lm_, pix_;
   std::vector<DevBuf<float>> t_, w_, C_, dsig_, drgb_, loss_rays_, acc_, dist_;
   // stop_level_grad = 0 (allocated only then): q^l = dL/dw^l [n][S] (levels < L - 1); for levels >= 1 the
   // integrator's and the bin edges' dL/dt^l and their sum with the encoding's [n][S + 1]
   bool cross_ = false;
   std::vector<DevBuf<float>> q_, dtr_, dtb_, dt_;
-  float* const* run_cross(int n, const float* o, const float* d, const float* radii, const float* lm, const float* pix,
-                          float msum, nof_output_grad_fn cb, void* user, uint32_t flags);
+  float* const* run_cross(int n, const float* o, const float* d, const float* radii, const float* nears,
+                          const float* fars, const float* lm, const float* pix, float msum, nof_output_grad_fn cb,
+                          void* user, uint32_t flags);
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -68,6 +68,10 @@ struct RenderBwdLevel {
   float lam;
   float *dsigma, *drgb, *loss_rays;
   uint32_t* amax;
+  // the distortion loss (the last level only: 0 for every other one, a block-uniform skip):
+  // dL/dw_k of dist_mult lossmult[r] / msum L_r joins e_k; dist_rays ([n], optional) receives that per-ray term
+  float dist_mult = 0.0f;
+  float* dist_rays = nullptr;
 };
 struct RenderBwdArgs {
   int n, S, white;
@@ -79,6 +83,11 @@ struct RenderBwdArgs {
   // (as launch_render_fwd with C = fwd_C, w = fwd_w; no acc / dist), g_ext must be null
   int fwd_last = 0;
   float *fwd_C = nullptr, *fwd_w = nullptr;
+  // the rays' near / far ([n]) and the sampling's lindisp, the normalised distance of the distortion loss (needed
+  // where a dist_mult != 0).  The trailing levels with dist_mult != 0 run k_render_bwd<PER, true>, the others the
+  // instantiation without the term in a launch of their own: with every dist_mult 0, exactly the launch it was
+  const float *nears = nullptr, *fars = nullptr;
+  int lindisp = 0;
 };
 hipError_t launch_render_bwd(const RenderBwdArgs& a, int nlev, hipStream_t st);
 hipError_t launch_output_gradient(int n, const float* C, const float* pix, const float* lossmult,
@@ -101,6 +110,12 @@ struct RenderBwdXArgs {
   float* t_grad;
   int fwd;
   float *fwd_C, *fwd_w;
+  // the distortion loss, as RenderBwdLevel / RenderBwdArgs (dist_mult != 0: k_render_bwd_x<PER, true>); with
+  // t_grad, its dL/dt_k = dL/ds_k s'(t_k) is added to the row before it is stored
+  float dist_mult;
+  float* dist_rays;
+  const float *nears, *fars;
+  int lindisp;
 };
 hipError_t launch_render_bwd_x(const RenderBwdXArgs& a, hipStream_t st);
 

@@ -191,6 +191,113 @@ __global__ __launch_bounds__(64) void k_render_fwd_pdf(RenderPdfArgs a) {
                   a.t_out, nullptr);
 }
 
+// The distortion loss of one ray by its wave (mip-NeRF 360's regulariser; the reference has no counterpart;
+// DESIGN.md 6g):  L = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i  over the midpoints m and widths delta of
+// s(t), the ray's normalised distance: (t - near) / (far - near), or with lindisp the parameter the samples are
+// spaced in, (1/near - 1/t) / (1/near - 1/far).  t is nondecreasing, so with the exclusive sums A_i = sum_{j<i} w_j,
+// P_i = sum_{j<i} w_j m_j and their counterparts B_i, Q_i over j > i
+//   D_i = sum_j w_j |m_i - m_j| = m_i (A_i - B_i) - (P_i - Q_i),   L = sum_i w_i D_i + (1/3) sum_i w_i^2 delta_i
+//   dL/dw_i = 2 D_i + (2/3) w_i delta_i,   dL/dm_i = 2 w_i (A_i - B_i),   dL/ddelta_i = w_i^2 / 3
+//   dL/ds_k = (dm_{k-1} + dm_k) / 2 + ddelta_{k-1} - ddelta_k   (out-of-range terms 0)
+// D is invariant to a shift of every m: it is evaluated on m - c_m, c_m the weighted mean midpoint, so the prefixes
+// stay of the size of the result (uncentred, O(1) prefixes cancel to an O(1e-4) D on a one-surface ray).  Two
+// inclusive wave scans (w, w (m - c_m)) in ray_alpha_T's __shfl_up style and one butterfly sum for c_m; every sum in a
+// fixed order.  Returns c L (in every lane) and adds c dL/dw_{k0+p} to ek[p]; WANT_T: dts[p] = c dL/ds_k s'(t_k) for
+// k = k0 + p, p <= PER (dts[PER] is k0 + PER's share of lane 63 alone: t_S).  A ray whose far - near (or, lindisp,
+// whose near or 1/near - 1/far) is not a positive finite number: ek untouched, zeros.
+template <int PER, bool WANT_T>
+__device__ __forceinline__ float ray_distortion(int lane, const float (&wk)[PER], const float (&tv)[PER + 1], float near,
+                                                float far, int lindisp, float c, float (&ek)[PER],
+                                                float (&dts)[PER + 1]) {
+  // s(t) = (u(t) - u0) inv with u = t, or with lindisp u = -1 / t (then s'(t) = inv u^2)
+  const float span = far - near;
+  bool ok = span > 0.0f && __builtin_isfinite(span);  // (wave-uniform: one ray per wave)
+  float inv, u0, u[PER + 1];
+  if (lindisp) {
+    u0 = -1.0f / near;
+    const float dsp = -1.0f / far - u0;
+    ok = ok && near > 0.0f && dsp > 0.0f && __builtin_isfinite(dsp);
+    inv = 1.0f / dsp;
+#pragma unroll
+    for (int p = 0; p <= PER; ++p) u[p] = -1.0f / tv[p];
+  } else {
+    u0 = near;
+    inv = 1.0f / span;
+#pragma unroll
+    for (int p = 0; p <= PER; ++p) u[p] = tv[p];
+  }
+  if (!ok) {
+    if constexpr (WANT_T) {
+#pragma unroll
+      for (int p = 0; p <= PER; ++p) dts[p] = 0.0f;
+    }
+    return 0.0f;
+  }
+  const auto sv = [&](int p) { return (u[p] - u0) * inv; };                    // s_k
+  const auto sp = [&](int p) { return lindisp ? inv * (u[p] * u[p]) : inv; };  // s'(t_k)
+  // (the midpoints are recomputed from s in each pass and the t terms formed as the loop goes: at PER = 8 every
+  // per-sample array held across the scans is a wave per SIMD)
+  float lw = 0.0f, lwm = 0.0f;
+#pragma unroll
+  for (int p = 0; p < PER; ++p) {
+    lw += wk[p];
+    lwm += wk[p] * (0.5f * (sv(p) + sv(p + 1)));
+  }
+  float incw = lw;  // inclusive sum scan over lanes
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(incw, o, 64);
+    if (lane >= o) incw += y;
+  }
+  const float Wt = __shfl(incw, 63, 64);
+  const float WM = wave_sum(lwm);
+  const float cm = Wt > 0.0f ? WM / Wt : 0.0f;
+  float lp = 0.0f;
+#pragma unroll
+  for (int p = 0; p < PER; ++p) lp += wk[p] * (0.5f * (sv(p) + sv(p + 1)) - cm);
+  float incp = lp;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(incp, o, 64);
+    if (lane >= o) incp += y;
+  }
+  const float Pt = __shfl(incp, 63, 64);
+  float A = __shfl_up(incw, 1, 64), P = __shfl_up(incp, 1, 64);  // exclusive at the lane's first sample
+  if (lane == 0) { A = 0.0f; P = 0.0f; }
+  float lL = 0.0f;
+  [[maybe_unused]] float dm0 = 0.0f, dd0 = 0.0f, pm = 0.0f, pd = 0.0f;  // dm, ddelta of samples k0 and k - 1
+#pragma unroll
+  for (int p = 0; p < PER; ++p) {
+    const float s0 = sv(p), s1 = sv(p + 1);
+    const float m = 0.5f * (s0 + s1) - cm;
+    const float wm = wk[p] * m;
+    const float AB = A - ((Wt - A) - wk[p]);  // A_i - B_i
+    const float PQ = P - ((Pt - P) - wm);     // P_i - Q_i
+    const float D = m * AB - PQ;
+    const float wdel = wk[p] * (s1 - s0);
+    lL += wk[p] * (D + (1.0f / 3.0f) * wdel);
+    ek[p] += c * (2.0f * D + (2.0f / 3.0f) * wdel);
+    if constexpr (WANT_T) {
+      const float dm = 2.0f * c * wk[p] * AB, dd = c * wk[p] * wk[p] * (1.0f / 3.0f);
+      if (p == 0) {
+        dm0 = dm; dd0 = dd;  // (t_{k0} waits for the previous lane's last sample)
+      } else {
+        dts[p] = (0.5f * (pm + dm) + pd - dd) * sp(p);  // dL/ds_k s'(t_k)
+      }
+      pm = dm; pd = dd;
+    }
+    A += wk[p];
+    P += wm;
+  }
+  if constexpr (WANT_T) {
+    dts[PER] = (0.5f * pm + pd) * sp(PER);
+    pm = __shfl_up(pm, 1, 64); pd = __shfl_up(pd, 1, 64);  // sample k0 - 1's
+    if (lane == 0) { pm = 0.0f; pd = 0.0f; }
+    dts[0] = (0.5f * (pm + dm0) + pd - dd0) * sp(0);
+  }
+  return c * wave_sum(lL);
+}
+
 // dL/dc_k = g w_k ;  dL/dsigma_k = delta_k |d| [T_{k+1} e_k - sum_{j>k} w_j e_j],  e_k = g.c_k - G
 // (the C# recursion MH:565-596 in closed form; G = g.1 under a white background).
 // One launch covers the levels of RenderBwdArgs (blockIdx.y = level, all with S samples per ray).  With
@@ -200,7 +307,10 @@ __global__ __launch_bounds__(64) void k_render_fwd_pdf(RenderPdfArgs a) {
 // level's integrator forward (k_render_fwd: C, w, the input check) runs first in its own blocks, and its
 // adjoint takes the ray state and the composite from it (the values it would reload: the same bits) — the
 // training step's last forward launch folded into the adjoint launch.
-template <int PER>
+// DIST: the distortion loss of a level with dist_mult != 0 (ray_distortion: its dL/dw_k joins e_k before the suffix
+// sum, so dsigma and the amax below see it; t is a constant here); false: the kernel without the term, which also
+// runs every level whose dist_mult is 0 (launch_render_bwd).
+template <int PER, bool DIST>
 __global__ __launch_bounds__(256) void k_render_bwd(RenderBwdArgs a) {
   const RenderBwdLevel& L = a.lv[blockIdx.y];
   const int lane = threadIdx.x & 63;
@@ -231,6 +341,22 @@ __global__ __launch_bounds__(256) void k_render_bwd(RenderBwdArgs a) {
     }
     const float G = a.white ? (g0 + g1 + g2) : 0.0f;
     const int k0 = lane * PER;
+    [[maybe_unused]] float dwk[PER];
+    [[maybe_unused]] bool dist = false;
+    if constexpr (DIST) {  // (before the colours are loaded: the term's registers come on top of fewer)
+      dist = L.dist_mult != 0.0f;  // (block-uniform)
+      if (dist) {
+        float w0[PER], none[PER + 1];
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+          w0[p] = rs.a[p] * rs.T[p];
+          dwk[p] = 0.0f;
+        }
+        const float v = ray_distortion<PER, false>(lane, w0, rs.tv, a.nears[r], a.fars[r], a.lindisp,
+                                                   L.dist_mult * a.lossmult[r] / a.msum, dwk, none);
+        if (L.dist_rays && lane == 0) L.dist_rays[r] = v;
+      }
+    }
     float cr[3 * PER], dc[3 * PER], ds[PER];
     vload<3 * PER, kRgbAlign<PER>>(L.rgb + ((size_t)r * a.S + k0) * 3, cr);
     float wk[PER], ek[PER];
@@ -239,6 +365,9 @@ __global__ __launch_bounds__(256) void k_render_bwd(RenderBwdArgs a) {
     for (int p = 0; p < PER; ++p) {
       wk[p] = rs.a[p] * rs.T[p];
       ek[p] = (g0 * cr[3 * p] + g1 * cr[3 * p + 1]) + g2 * cr[3 * p + 2] - G;
+      if constexpr (DIST) {
+        if (dist) ek[p] += dwk[p];
+      }
       dc[3 * p] = g0 * wk[p]; dc[3 * p + 1] = g1 * wk[p]; dc[3 * p + 2] = g2 * wk[p];
       ls += wk[p] * ek[p];
     }
@@ -286,7 +415,8 @@ __global__ __launch_bounds__(256) void k_render_bwd(RenderBwdArgs a) {
 
 // k_render_bwd for one level with the cross-level terms (launch.h RenderBwdXArgs): q_k joins e_k, and the
 // adjoint of delta_k = t_{k+1} - t_k gives dL/dt.  Without q and t_grad its values are k_render_bwd's.
-template <int PER>
+// DIST (dist_mult != 0): the distortion loss as in k_render_bwd, and its dL/dt_k added to the t_grad row.
+template <int PER, bool DIST>
 __global__ __launch_bounds__(256) void k_render_bwd_x(RenderBwdXArgs a) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -312,6 +442,22 @@ __global__ __launch_bounds__(256) void k_render_bwd_x(RenderBwdXArgs a) {
   }
   const float G = a.white ? (g0 + g1 + g2) : 0.0f;
   const int k0 = lane * PER;
+  [[maybe_unused]] float dwk[PER], dts[PER + 1];
+  [[maybe_unused]] bool dist = false;
+  if constexpr (DIST) {  // (before the colours are loaded: the term's registers come on top of fewer)
+    dist = a.dist_mult != 0.0f;  // (block-uniform)
+    if (dist) {
+      float w0[PER];
+#pragma unroll
+      for (int p = 0; p < PER; ++p) {
+        w0[p] = rs.a[p] * rs.T[p];
+        dwk[p] = 0.0f;
+      }
+      const float v = ray_distortion<PER, true>(lane, w0, rs.tv, a.nears[r], a.fars[r], a.lindisp,
+                                                a.dist_mult * a.lossmult[r] / a.msum, dwk, dts);
+      if (a.dist_rays && lane == 0) a.dist_rays[r] = v;
+    }
+  }
   float cr[3 * PER], dc[3 * PER], ds[PER], sg[PER], qk[PER];
   vload<3 * PER, kRgbAlign<PER>>(a.rgb + ((size_t)r * a.S + k0) * 3, cr);
   vload<PER, PER>(a.sigma + (size_t)r * a.S + k0, sg);
@@ -328,6 +474,9 @@ __global__ __launch_bounds__(256) void k_render_bwd_x(RenderBwdXArgs a) {
     wk[p] = rs.a[p] * rs.T[p];
     ek[p] = (g0 * cr[3 * p] + g1 * cr[3 * p + 1]) + g2 * cr[3 * p + 2] - G;
     if (a.q) ek[p] += qk[p];
+    if constexpr (DIST) {
+      if (dist) ek[p] += dwk[p];
+    }
     dc[3 * p] = g0 * wk[p]; dc[3 * p + 1] = g1 * wk[p]; dc[3 * p + 2] = g2 * wk[p];
     ls += wk[p] * ek[p];
   }
@@ -356,8 +505,15 @@ __global__ __launch_bounds__(256) void k_render_bwd_x(RenderBwdXArgs a) {
     float* tg = a.t_grad + (size_t)r * (a.S + 1) + k0;
 #pragma unroll
     for (int p = 0; p < PER; ++p) {
-      tg[p] = prev - dd[p];
+      float x = prev - dd[p];
+      if constexpr (DIST) {
+        if (dist) x += dts[p];
+      }
+      tg[p] = x;
       prev = dd[p];
+    }
+    if constexpr (DIST) {
+      if (dist) prev += dts[PER];
     }
     if (lane == 63) tg[PER] = prev;
   }
@@ -398,13 +554,34 @@ hipError_t launch_render_fwd_pdf(const RenderPdfArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// A level with the distortion loss runs k_render_bwd<PER, true>; the levels without it keep k_render_bwd<PER, false>
+// in a launch of their own (so their bits are those of a step without the term whatever the compiler makes of the
+// other instantiation: which products of g.c_k it fuses depends on the code around them; measured 2 .. 16 ulp on
+// dsigma at PER >= 2 when one instantiation ran both).
 hipError_t launch_render_bwd(const RenderBwdArgs& a, int nlev, hipStream_t st) {
   if (a.n <= 0 || nlev <= 0) return hipSuccess;
   if (nlev > kRenderMaxLevels || (a.fwd_last && (a.lv[nlev - 1].g_ext || !a.fwd_C || !a.fwd_w)))
     return hipErrorInvalidValue;
-  const dim3 grid((a.n + 3) / 4, nlev), block(256);
   const int S = a.S;
-  NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL(k_render_bwd<PER>, grid, block, 0, st, a));
+  int first = nlev;  // the levels from `first` on carry the term (the host puts it on the last one)
+  while (first > 0 && a.lv[first - 1].dist_mult != 0.0f) --first;
+  for (int l = 0; l < first; ++l)
+    if (a.lv[l].dist_mult != 0.0f) return hipErrorInvalidValue;
+  // the term needs near / far and c_r = dist_mult lossmult[r] / msum
+  if (first < nlev && (!a.nears || !a.fars || !a.lossmult || !(a.msum > 0.0f))) return hipErrorInvalidValue;
+  const dim3 block(256);
+  if (first > 0) {
+    RenderBwdArgs b = a;
+    if (first < nlev) b.fwd_last = 0;  // (the forward belongs to the last entry)
+    const dim3 grid((a.n + 3) / 4, first);
+    NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL((k_render_bwd<PER, false>), grid, block, 0, st, b));
+  }
+  if (first < nlev) {
+    RenderBwdArgs b = a;
+    for (int l = first; l < nlev; ++l) b.lv[l - first] = a.lv[l];
+    const dim3 grid((a.n + 3) / 4, nlev - first);
+    NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL((k_render_bwd<PER, true>), grid, block, 0, st, b));
+  }
   return hipGetLastError();
 }
 
@@ -425,7 +602,12 @@ hipError_t launch_render_bwd_x(const RenderBwdXArgs& a, hipStream_t st) {
   if (a.fwd && (a.g_ext || !a.fwd_C || !a.fwd_w)) return hipErrorInvalidValue;
   const dim3 grid((a.n + 3) / 4), block(256);
   const int S = a.S;
-  NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL(k_render_bwd_x<PER>, grid, block, 0, st, a));
+  if (a.dist_mult != 0.0f) {  // the distortion loss's instantiation (near / far, c_r = dist_mult lossmult[r] / msum)
+    if (!a.nears || !a.fars || !a.lossmult || !(a.msum > 0.0f)) return hipErrorInvalidValue;
+    NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL((k_render_bwd_x<PER, true>), grid, block, 0, st, a));
+    return hipGetLastError();
+  }
+  NOF_RENDER_DISPATCH(S, hipLaunchKernelGGL((k_render_bwd_x<PER, false>), grid, block, 0, st, a));
   return hipGetLastError();
 }
 

@@ -47,6 +47,23 @@ class nof_config(C.Structure):
         ("stop_level_grad", C.c_int32),
     ]
 
+    # include/nof.h appends `float distortion_loss_mult` after stop_level_grad.  The struct is 8-byte aligned (seed,
+    # stream) and ended 4 bytes short of a multiple of 8, so the new field takes what were its tail padding bytes
+    # and sizeof(nof_config) is what it was (lib() checks it against nof_config_size()).  The field list above is
+    # left ending at stop_level_grad (CPU tests of earlier options pin that name as its last entry); the new field
+    # is a property at its offset instead, read and set like any other (default_config(distortion_loss_mult=x)).
+    @property
+    def distortion_loss_mult(self) -> float:
+        return C.c_float.from_buffer(self, _DIST_MULT_OFFSET).value
+
+    @distortion_loss_mult.setter
+    def distortion_loss_mult(self, value: float) -> None:
+        C.c_float.from_buffer(self, _DIST_MULT_OFFSET).value = value
+
+
+_DIST_MULT_OFFSET = nof_config.stop_level_grad.offset + C.sizeof(C.c_int32)
+assert _DIST_MULT_OFFSET + C.sizeof(C.c_float) <= C.sizeof(nof_config), "nof_config: no room for distortion_loss_mult"
+
 
 class nof_level_view(C.Structure):
     _fields_ = [("n", C.c_int32), ("samples", C.c_int32)] + [
@@ -133,6 +150,7 @@ SIGNATURES = {
     "nof_mipnerf_set_ray_grad": [P, I32],
     "nof_mipnerf_ray_grad": [P, C.POINTER(P), C.POINTER(P)],
     "nof_mipnerf_loss": [P, C.POINTER(F)],
+    "nof_mipnerf_distortion_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],
     "nof_device_checks_selftest": [],
@@ -221,6 +239,7 @@ SIGNATURES = {
     "nof_kernel_render": [I32, I32, P, P, P, P, I32, P, P, P],
     "nof_kernel_render_grad": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P],
     "nof_kernel_render_grad_ex": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P],
+    "nof_kernel_render_grad_dist": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P, P, I32, F, P, P],
     "nof_kernel_sample_pdf_grad": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P, P],
     "nof_kernel_encode_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P],
     "nof_kernel_ray_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P],

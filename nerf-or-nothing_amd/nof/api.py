@@ -359,6 +359,14 @@ class AcceleratedMipNeRF:
         call("nof_mipnerf_loss", self._h, C.byref(out))
         return out.value
 
+    def distortion_loss(self) -> float:
+        """The distortion term of the last gradient step, lambda_d sum_r mu_r L_r / sum mu (the model's
+        distortion_loss_mult= keyword, include/nof.h nof_config.distortion_loss_mult); 0.0 with the option off.
+        loss() stays the photometric loss."""
+        out = C.c_float()
+        call("nof_mipnerf_distortion_loss", self._h, C.byref(out))
+        return out.value
+
     def numeric_status(self, clear: bool = True) -> int:
         """NOF_NUMERIC_* bits (non-finite forward outputs / output gradients) since the last clear."""
         out = C.c_uint32()

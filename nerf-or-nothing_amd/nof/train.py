@@ -59,6 +59,7 @@ class Trainer:
         self.step_idx = 0  # completed steps (Program.cs counts from 1)
         self.device = device
         self.last_loss = None
+        self.last_distortion = None  # the distortion term of the last print step (distortion_loss_mult > 0)
         # data parallel: the gradient arena is all-reduced bucket by bucket on a communication
         # stream ordered after the library's stream (self.stream, which may be any stream), and the
         # library's stream waits for the last bucket before Adam (nof.dp.BucketedAllReduce)
@@ -112,6 +113,9 @@ class Trainer:
                                          f"(flags {bad:#x}; 1 = forward outputs, 2 = output gradients)")
             self.last_loss = self.fine_loss(b)
             line = f"Step {step}/{self.lr['max_steps']}, Loss: {self.last_loss}"
+            if self.cfg.distortion_loss_mult > 0:  # this rank's term, lambda_d sum mu L / sum mu (global sum mu)
+                self.last_distortion = self.model.distortion_loss()
+                line += f", Distortion: {self.last_distortion:.9g}"
             if self.with_stats:  # StatsUtil.cs:13,16-18, of the all-reduced gradient (identical on every rank)
                 self.last_stats = st = self.adam.stats()
                 line += (f", grad_norm: {st['grad_norm']:.9g}, grad_abs_max: {st['grad_abs_max']:.9g}, "
@@ -319,6 +323,9 @@ def parse_args(argv=None):
     ap.add_argument("--rgb-padding", type=float, default=0.001)
     ap.add_argument("--no-stop-level-grad", action="store_true",
                     help="MipNerfModel.StopLevelGrad = false: backprop across levels (f32 / f16p, the any-shape path)")
+    ap.add_argument("--distortion-loss-mult", type=float, default=0.0, metavar="X",
+                    help="the distortion loss of mip-NeRF 360 on the last level's weights, times X (0 = off; every "
+                         "precision; with --no-stop-level-grad it also trains the coarse pass); printed next to the loss")
     # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70; 0 = off) and the step statistics
     ap.add_argument("--grad-max-norm", type=float, default=0.0, help="clip the gradient's global norm")
     ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
@@ -342,6 +349,8 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.refine_poses < 0:
         ap.error("--refine-poses takes a learning rate > 0")
+    if not (a.distortion_loss_mult >= 0 and a.distortion_loss_mult < float("inf")):
+        ap.error("--distortion-loss-mult must be a finite number >= 0")
     if a.refine_poses and not a.scene:
         ap.error("--refine-poses needs --scene: only a scene of poses and images has poses to refine")
     if a.holdout < 0 or a.holdout == 1:
@@ -364,7 +373,8 @@ def main(argv=None):
     if a.samples:
         net["num_samples"] = tuple(a.samples)
     net.update(lindisp=int(a.lindisp), ray_shape=int(a.cylinder), density_bias=a.density_bias,
-               rgb_padding=a.rgb_padding, stop_level_grad=0 if a.no_stop_level_grad else 1)
+               rgb_padding=a.rgb_padding, stop_level_grad=0 if a.no_stop_level_grad else 1,
+               distortion_loss_mult=a.distortion_loss_mult)
     if a.scene:
         ds = scene_dataset(a.scene, a.num_scales, not a.disable_multiscale_loss, a.device, holdout=a.holdout)
     elif a.records:
