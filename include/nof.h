@@ -234,7 +234,9 @@ nof_status nof_mipnerf_level_view(nof_mipnerf* h, int32_t level, nof_level_view*
 /* stop_level_grad = 0: borrowed device views of the last step's cross-level terms (tests and tooling):
  * *w_grad = q^level [n][S] = dL/dw^level from level + 1's resampler (NULL for the last level), *t_grad =
  * dL/dt^level [n][S + 1] = integrator + encoding + bin-edge terms (NULL for level 0, whose t is a constant).
- * Both NULL with stop_level_grad = 1. */
+ * Both NULL with stop_level_grad = 1, unless the interlevel loss is on (nof_mipnerf_set_interlevel_loss): then
+ * *w_grad = q^level holds that loss's dL/dw^level (at stop_level_grad = 0 added to the resampler's) for every
+ * level but the last, and *t_grad stays NULL at stop_level_grad = 1. */
 nof_status nof_mipnerf_cross_view(nof_mipnerf* h, int32_t level, const float** w_grad, const float** t_grad);
 /* Ray gradients, for camera refinement: with the option on, every step also leaves dL/d origins and
  * dL/d directions of its own rays (radius, near, far, the t-values and the Philox uniforms held constant).
@@ -253,6 +255,22 @@ nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out);
  * gradient entry; the per-ray terms summed on the host in ray order; synchronises).  0 with the option off;
  * NOF_ERR_INVALID_ARG before a step. */
 nof_status nof_mipnerf_distortion_loss(nof_mipnerf* h, float* out);
+/* The interlevel (proposal) loss of mip-NeRF 360 (no counterpart in the reference).  mult = lambda_p
+ * >= 0, 0 = off (the default: every launch as without the option).  For every level l < num_levels - 1 the
+ * objective gains lambda_p sum_r mu_r L_r^l / sum mu with
+ *   L_r^l = sum_i max(0, w_i - bound_i)^2 / (w_i + 2^-23),
+ * (t, w) the LAST level's intervals and weights, a constant of the backward (also at stop_level_grad = 0), and
+ * bound_i the sum of level l's weights over its intervals that touch [t_i, t_{i+1}] (the published lossfun_outer):
+ * level l's weight histogram is pushed to be an upper envelope of the last level's.  The term has a gradient in
+ * level l's weights only; it joins that level's integrator adjoint as q^l.  Every precision mode, network and both
+ * gradient entries; with stop_level_grad = 0 it is added to the q^l of the resampler adjoint.  The levels share one
+ * MLP (mip-NeRF): this is 360's loss, not its separate proposal network.  nof_config is not extended (its tail
+ * padding is used up): the option is this setter.  num_levels == 1: a no-op.  Negative or non-finite:
+ * NOF_ERR_INVALID_ARG (interlevel_loss_mult).  The first mult > 0 allocates q^l and the per-ray terms. */
+nof_status nof_mipnerf_set_interlevel_loss(nof_mipnerf* h, float mult);
+/* its term of the last gradient step, summed on the host in level order, then ray order (synchronises); 0 with the
+ * option off; NOF_ERR_INVALID_ARG before a step.  nof_mipnerf_loss stays the photometric loss. */
+nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
  * stated limit: an overflow surfaces here instead of silently): NOF_NUMERIC_FORWARD = a training
  * forward produced a non-finite composite colour; NOF_NUMERIC_DELTA = the f16x2 delta scaling saw a
@@ -679,6 +697,16 @@ nof_status nof_kernel_render_grad_dist(int32_t n, int32_t samples, const float* 
                                        const float* dev_w_grad, float* dev_t_grad, const float* nears,
                                        const float* fars, int32_t lindisp, float dist_mult, float* dev_dist_rays,
                                        void* stream);
+/* k_interlevel (nof_mipnerf_set_interlevel_loss): dev_w_grad [n][samples_prop] = d/dw_prop of
+ * mult loss_mults[r] / loss_mult_sum L_r, the proposal (t_prop [n][samples_prop + 1], w_prop [n][samples_prop])
+ * against the target (t_tgt [n][samples_tgt + 1], w_tgt [n][samples_tgt]); accumulate = 1 adds to dev_w_grad, 0
+ * overwrites it; dev_rays ([n] or NULL) receives the per-ray term.  Both sample counts in {64, 128, 256, 512},
+ * mult >= 0 (0: zeros), loss_mult_sum > 0; n = 0 launches nothing.  Every sum in a fixed order: the same bits
+ * run to run. */
+nof_status nof_kernel_interlevel(int32_t n, int32_t samples_prop, const float* t_prop, const float* w_prop,
+                                 int32_t samples_tgt, const float* t_tgt, const float* w_tgt, const float* loss_mults,
+                                 float loss_mult_sum, float mult, int32_t accumulate, float* dev_w_grad,
+                                 float* dev_rays, void* stream);
 /* The adjoint of nof_kernel_sample_pdf (the same sampling arguments; the forward's bin index, clamps, cdf
  * saturation, pad branch and blur-pool max picks are recomputed and held): dev_t_out_grad [n][S_out + 1] ->
  * dev_w_grad [n][S_in] and dev_t_in_grad [n][S_in + 1] (or NULL: not wanted), both overwritten. */

@@ -40,6 +40,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,6 +69,7 @@ struct Args {
   float density_bias = -1.0f, rgb_padding = 0.001f;
   bool no_stop_level_grad = false;  // MipNerfModel.StopLevelGrad = false (MipNerfModel.cs:13)
   float distortion_loss_mult = 0.0f;  // nof_config.distortion_loss_mult (0 = off)
+  float interlevel_loss_mult = 0.0f;  // nof_mipnerf_set_interlevel_loss (0 = off)
   // Config (TrainState.cs:54-58)
   float lr_init = 5e-4f, lr_final = 5e-6f, lr_delay_mult = 0.01f;
   int max_steps = 1000000, lr_delay_steps = 2500;
@@ -86,7 +88,7 @@ struct Args {
                "                 [--samples S0,S1[,...]]  (e.g. BASELINE configs[0]: --net-depth 4 --net-width 128 "
                "--samples 64,64)\n"
                "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n"
-               "                 [--no-stop-level-grad] [--distortion-loss-mult X]\n"
+               "                 [--no-stop-level-grad] [--distortion-loss-mult X] [--interlevel-loss-mult X]\n"
                "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n");
   std::exit(code);
 }
@@ -121,6 +123,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--rgb-padding") a.rgb_padding = std::strtof(val(), nullptr);
     else if (k == "--no-stop-level-grad") a.no_stop_level_grad = true;
     else if (k == "--distortion-loss-mult") a.distortion_loss_mult = std::strtof(val(), nullptr);
+    else if (k == "--interlevel-loss-mult") a.interlevel_loss_mult = std::strtof(val(), nullptr);
     else if (k == "--grad-max-norm") a.grad_max_norm = std::strtof(val(), nullptr);
     else if (k == "--grad-max-val") a.grad_max_val = std::strtof(val(), nullptr);
     else if (k == "--weight-decay") a.weight_decay = std::strtof(val(), nullptr);
@@ -161,6 +164,10 @@ Args parse(int argc, char** argv) {
   }
   if (a.records.empty() || a.steps < 0 || a.batch <= 0 || a.print_every < 0 || a.save_every < 0) usage(2);
   if (a.save_every && a.ckpt_dir.empty()) usage(2);
+  if (!(a.interlevel_loss_mult >= 0.0f && a.interlevel_loss_mult <= FLT_MAX)) {  // (also NaN)
+    std::fprintf(stderr, "nof_train: --interlevel-loss-mult must be a finite number >= 0\n");
+    usage(2);
+  }
   if (a.gpus < 0 || (a.gpus > 0 && a.batch % a.gpus)) usage(2);
   const int shard = a.batch / (a.gpus > 0 ? a.gpus : 1);
   if (a.micro < 0 || (a.micro > 0 && shard % a.micro)) usage(2);
@@ -276,6 +283,7 @@ int main(int argc, char** argv) {
     // overlapped) and grouped all-reduces then give bitwise-identical parameters
     R.cfg.grad_buckets = G > 1 ? 1 : 0;
     CHECK(nof_mipnerf_create(&R.cfg, &R.model));
+    if (a.interlevel_loss_mult > 0.0f) CHECK(nof_mipnerf_set_interlevel_loss(R.model, a.interlevel_loss_mult));
     int32_t sizes[64], nsizes = 0;
     CHECK(nof_mipnerf_layer_sizes(R.model, sizes, 64, &nsizes));
     CHECK(nof_adam_create(sizes, nsizes, &R.cfg, &R.adam));
@@ -389,6 +397,16 @@ int main(int argc, char** argv) {
           dist += (double)x;
         }
         std::printf(", Distortion: %.9g", dist);
+      }
+      if (a.interlevel_loss_mult > 0.0f) {  // as the distortion term: summed over the replicas
+        double prop = 0.0;
+        for (Replica& R : rs) {
+          float x = 0.0f;
+          CHECK(nof_set_device(R.device));
+          CHECK(nof_mipnerf_interlevel_loss(R.model, &x));
+          prop += (double)x;
+        }
+        std::printf(", Interlevel: %.9g", prop);
       }
       if (with_stats) {  // of the all-reduced gradient: the same record on every replica
         nof_step_stats st;

@@ -245,6 +245,18 @@ nof_status nof_mipnerf_loss(nof_mipnerf* h, float* out) {
 nof_status nof_mipnerf_distortion_loss(nof_mipnerf* h, float* out) {
   return guard([&] { ARG(h && out); DEV(h); *out = h->impl->distortion_loss(); });
 }
+nof_status nof_mipnerf_set_interlevel_loss(nof_mipnerf* h, float mult) {
+  return guard([&] {
+    ARG(h);
+    if (!(std::isfinite(mult) && mult >= 0.0f))
+      throw Error(NOF_ERR_INVALID_ARG, "invalid argument: interlevel_loss_mult must be finite and >= 0");
+    DEV(h);
+    h->impl->set_interlevel_loss(mult);
+  });
+}
+nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out) {
+  return guard([&] { ARG(h && out); DEV(h); *out = h->impl->interlevel_loss(); });
+}
 nof_status nof_mipnerf_render_device(nof_mipnerf* h, int32_t n, const float* o, const float* d, const float* radii,
                                      const float* nears, const float* fars, int32_t randomized, int32_t white_bkgd,
                                      nof_render_out* out) {
@@ -788,6 +800,20 @@ nof_status nof_kernel_render_grad_dist(int32_t n, int32_t S, const float* sigma,
     a.q = w_grad; a.t_grad = t_grad;
     a.dist_mult = dist_mult; a.dist_rays = dist_rays; a.nears = nears; a.fars = fars; a.lindisp = lindisp;
     NOF_HIP(nof::launch_render_bwd_x(a, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_interlevel(int32_t n, int32_t S_prop, const float* t_prop, const float* w_prop, int32_t S_tgt,
+                                 const float* t_tgt, const float* w_tgt, const float* lm, float msum, float mult,
+                                 int32_t accumulate, float* w_grad, float* rays, void* stream) {
+  return guard([&] {
+    auto ok = [](int32_t S) { return S == 64 || S == 128 || S == 256 || S == 512; };
+    ARG(n >= 0 && ok(S_prop) && ok(S_tgt) && t_prop && w_prop && t_tgt && w_tgt && lm && w_grad);
+    ARG(msum > 0.0f && std::isfinite(mult) && mult >= 0.0f && (accumulate == 0 || accumulate == 1));
+    nof::InterlevelArgs a{};
+    a.n = n; a.S_prop = S_prop; a.S_tgt = S_tgt; a.accumulate = accumulate;
+    a.t_prop = t_prop; a.w_prop = w_prop; a.t_tgt = t_tgt; a.w_tgt = w_tgt; a.lossmult = lm; a.msum = msum;
+    a.mult = mult; a.w_grad = w_grad; a.rays = rays;
+    NOF_HIP(nof::launch_interlevel(a, (hipStream_t)stream));
   });
 }
 nof_status nof_kernel_sample_pdf_grad(int32_t n, int32_t S_in, const float* t_in, const float* w, int32_t S_out,

@@ -1341,6 +1341,7 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
   if (cross_) {
     float* const* g = run_cross(n, o, d, radii, nears, fars, lm, pix, msum, cb_in, user, flags);
     dist_valid_ = true;
+    prop_valid_ = true;
     last_n_ = n;
     last_fused_ = cb_in == nullptr;
     ++step_;
@@ -1350,7 +1351,9 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
   // MNcpp:125-134: the loss gradient and the integrator adjoint of every level (with the f16 modes' delta
   // maxima), levels of equal sample count in one launch when no callback supplies dL/dC, else one level
   // at a time after its callback
-  {
+  if (prop_mult_ > 0.0f && L >= 2) {
+    run_interlevel(n, d, nears, fars, lm, pix, msum, cb, user);
+  } else {
     nof::RenderBwdArgs ra{};
     ra.n = n; ra.d = d; ra.white = cfg_.white_bkgd; ra.pix = pix; ra.lossmult = lm; ra.msum = msum;
     ra.nonfinite = mlp->numeric_flags();
@@ -1397,10 +1400,76 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
     grads = mlp->get_gradient_levels(cg.data(), dg.data(), flags);
   }
   dist_valid_ = true;
+  prop_valid_ = true;
   last_n_ = n;
   last_fused_ = cb == nullptr;
   ++step_;
   return grads;
+}
+
+void AcceleratedMipNeRF::launch_interlevel_level(int n, int l, const float* lm, float msum, int accumulate) {
+  const int L = cfg_.num_levels;
+  nof::InterlevelArgs ia{};
+  ia.n = n; ia.S_prop = cfg_.num_samples[l]; ia.S_tgt = cfg_.num_samples[L - 1]; ia.accumulate = accumulate;
+  ia.t_prop = t_[l].p; ia.w_prop = w_[l].p; ia.t_tgt = t_[L - 1].p; ia.w_tgt = w_[L - 1].p;
+  ia.lossmult = lm; ia.msum = msum; ia.mult = prop_mult_;
+  ia.w_grad = q_[l].p; ia.rays = prop_rays_[l].p;
+  timer.begin(kTRenderBwd);
+  NOF_HIP(nof::launch_interlevel(ia, st_));
+  timer.end(kTRenderBwd);
+}
+
+// The integrator adjoints of a stop_level_grad = 1 step with the interlevel loss (L >= 2): the last
+// level alone through launch_render_bwd, exactly as without the option (its fwd_last forward gives the target w);
+// k_interlevel per coarser level -> q^l; launch_render_bwd_x per coarser level with q = q^l and no t gradient.  The
+// coarser levels claim no amax word: the f16 modes take theirs from the launch_delta_amax fallback of bwd_args /
+// gen_backward.  With a callback the target's forward has run already, so k_interlevel goes first and the callbacks
+// keep their order 0 .. L - 1, each followed by its level's launch.
+void AcceleratedMipNeRF::run_interlevel(int n, const float* d, const float* nears, const float* fars, const float* lm,
+                                        const float* pix, float msum, nof_output_grad_fn cb, void* user) {
+  const int L = cfg_.num_levels;
+  auto last = [&](const float* g) {
+    const int lv = L - 1;
+    nof::RenderBwdArgs ra{};
+    ra.n = n; ra.S = cfg_.num_samples[lv]; ra.d = d; ra.white = cfg_.white_bkgd; ra.pix = pix; ra.lossmult = lm;
+    ra.msum = msum; ra.nonfinite = mlp->numeric_flags();
+    const float dmult = cfg_.distortion_loss_mult;
+    if (dmult > 0.0f) { ra.nears = nears; ra.fars = fars; ra.lindisp = cfg_.lindisp; }
+    nof::RenderBwdLevel& R = ra.lv[0];
+    R.sigma = mlp->density(lv); R.rgb = mlp->rgb(lv); R.t = t_[lv].p; R.C = C_[lv].p; R.g_ext = g; R.lam = 1.0f;
+    R.dsigma = dsig_[lv].p; R.drgb = drgb_[lv].p; R.loss_rays = cb ? nullptr : loss_rays_[lv].p;
+    R.amax = mlp->claim_delta_amax(lv);
+    R.dist_mult = dmult;
+    R.dist_rays = dmult > 0.0f ? dist_rays_.p : nullptr;
+    if (!cb) { ra.fwd_last = 1; ra.fwd_C = C_[lv].p; ra.fwd_w = w_[lv].p; }
+    timer.begin(kTRenderBwd);
+    NOF_HIP(nof::launch_render_bwd(ra, 1, st_));
+    timer.end(kTRenderBwd);
+  };
+  auto coarse = [&](int lv, const float* g) {
+    nof::RenderBwdXArgs ra{};
+    ra.n = n; ra.S = cfg_.num_samples[lv]; ra.white = cfg_.white_bkgd; ra.d = d; ra.pix = pix; ra.lossmult = lm;
+    ra.msum = msum; ra.nonfinite = mlp->numeric_flags();
+    ra.sigma = mlp->density(lv); ra.rgb = mlp->rgb(lv); ra.t = t_[lv].p; ra.C = C_[lv].p; ra.g_ext = g;
+    ra.lam = cfg_.coarse_loss_mult;
+    ra.dsigma = dsig_[lv].p; ra.drgb = drgb_[lv].p; ra.loss_rays = cb ? nullptr : loss_rays_[lv].p;
+    ra.q = q_[lv].p; ra.t_grad = nullptr;
+    timer.begin(kTRenderBwd);
+    NOF_HIP(nof::launch_render_bwd_x(ra, st_));
+    timer.end(kTRenderBwd);
+  };
+  if (!cb) {
+    last(nullptr);
+    for (int lv = 0; lv < L - 1; ++lv) launch_interlevel_level(n, lv, lm, msum, 0);
+    for (int lv = 0; lv < L - 1; ++lv) coarse(lv, nullptr);
+    return;
+  }
+  for (int lv = 0; lv < L - 1; ++lv) launch_interlevel_level(n, lv, lm, msum, 0);
+  for (int lv = 0; lv < L; ++lv) {
+    const float* g = reinterpret_cast<const float*>(cb(user, (uint64_t)(uintptr_t)C_[lv].p, lv, msum, (uint64_t)(uintptr_t)lm));
+    NOF_REQUIRE(g != nullptr, "output-gradient callback returned null");
+    if (lv < L - 1) coarse(lv, g); else last(g);
+  }
 }
 
 // stop_level_grad = 0: the backward of a step whose forward has run, levels descending.  Level l:
@@ -1428,6 +1497,8 @@ float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* 
     ra.dsigma = dsig_[lv].p; ra.drgb = drgb_[lv].p; ra.loss_rays = cb ? nullptr : loss_rays_[lv].p;
     ra.q = lv + 1 < L ? q_[lv].p : nullptr;
     ra.t_grad = lv >= 1 ? dtr_[lv].p : nullptr;
+    // the interlevel loss joins the q^l that level l + 1's resampler adjoint has written (the target a constant)
+    if (lv + 1 < L && prop_mult_ > 0.0f) launch_interlevel_level(n, lv, lm, msum, 1);
     if (lv == L - 1 && cfg_.distortion_loss_mult > 0.0f) {  // the distortion loss: dL/dw into e_k, dL/dt into dtr_
       ra.dist_mult = cfg_.distortion_loss_mult; ra.dist_rays = dist_rays_.p;
       ra.nears = nears; ra.fars = fars; ra.lindisp = cfg_.lindisp;
@@ -1471,9 +1542,39 @@ void AcceleratedMipNeRF::ray_grad(const float** o_grad, const float** d_grad) co
   *d_grad = mlp->ray_d_grad();
 }
 
+void AcceleratedMipNeRF::set_interlevel_loss(float mult) {
+  NOF_REQUIRE(std::isfinite(mult) && mult >= 0.0f, "interlevel_loss_mult must be finite and >= 0");
+  const int L = cfg_.num_levels;
+  if (mult > 0.0f && L >= 2 && prop_rays_.empty()) {  // first switched on: q^l (unless stop_level_grad = 0 has
+    const size_t N = cfg_.max_rays;                   // them) and the per-ray terms
+    prop_rays_.resize(L - 1);
+    for (int l = 0; l + 1 < L; ++l) prop_rays_[l].alloc(N);
+    if (q_.empty()) q_.resize(L);
+    for (int l = 0; l + 1 < L; ++l)
+      if (!q_[l].p) q_[l].alloc(N * (size_t)cfg_.num_samples[l]);
+  }
+  prop_mult_ = mult;
+  prop_valid_ = false;  // (the stored terms belong to a step with another multiplier)
+}
+
+float AcceleratedMipNeRF::interlevel_loss() {
+  const int L = cfg_.num_levels;
+  if (!(prop_mult_ > 0.0f) || L < 2) return 0.0f;
+  NOF_REQUIRE(prop_valid_ && last_n_ > 0, "the interlevel loss is available after a gradient step");
+  std::vector<float> h(last_n_);
+  double s = 0.0;
+  for (int l = 0; l + 1 < L; ++l) {  // (level order, then ray order)
+    NOF_HIP(hipMemcpyAsync(h.data(), prop_rays_[l].p, last_n_ * sizeof(float), hipMemcpyDeviceToHost, st_));
+    NOF_HIP(hipStreamSynchronize(st_));
+    for (float x : h) s += x;
+  }
+  return (float)s;
+}
+
 void AcceleratedMipNeRF::cross_view(int level, const float** w_grad, const float** t_grad) const {
   NOF_REQUIRE(level >= 0 && level < cfg_.num_levels, "level out of range");
-  *w_grad = cross_ ? q_[level].p : nullptr;
+  const bool prop = prop_mult_ > 0.0f && level + 1 < cfg_.num_levels;  // q^l holds the interlevel term
+  *w_grad = (cross_ || prop) ? q_[level].p : nullptr;
   *t_grad = cross_ ? dt_[level].p : nullptr;
 }
 
@@ -1504,6 +1605,7 @@ void AcceleratedMipNeRF::Render(int n, const float* o, const float* d, const flo
   last_n_ = n;
   last_fused_ = false;  // no loss for a render
   dist_valid_ = false;
+  prop_valid_ = false;
 }
 
 nof_level_view AcceleratedMipNeRF::level_view(int level) const {

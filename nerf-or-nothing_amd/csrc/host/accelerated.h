@@ -337,6 +337,12 @@ class AcceleratedMipNeRF {
   // nof_config.distortion_loss_mult's term of the last gradient step, lambda_d sum_r mu_r L_r / sum mu (0 with the
   // option off; synchronises)
   float distortion_loss();
+  // The interlevel (proposal) loss (include/nof.h nof_mipnerf_set_interlevel_loss): lambda_p >= 0, 0 =
+  // off (every launch as without the option); the first lambda_p > 0 allocates q^l and the per-ray terms.
+  void set_interlevel_loss(float mult);
+  // its term of the last gradient step, summed on the host in level order, then ray order (0 with the option off;
+  // synchronises)
+  float interlevel_loss();
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
   // per level comp_rgb [n][3], distance [n], acc [n] (device, borrowed until the next call).
@@ -365,10 +371,19 @@ class AcceleratedMipNeRF {
   bool ray_grad_valid_ = false;  // a step has run since the option was switched on
   bool dist_valid_ = false;      // the last call was a gradient step (dist_rays_ holds its rays' terms)
   DevBuf<float> dist_rays_;      // [max_rays]: c_r L_r of the last level (distortion_loss_mult > 0)
+  float prop_mult_ = 0.0f;       // lambda_p of the interlevel loss (0 = off)
+  bool prop_valid_ = false;      // a gradient step has run since it was set, and no render since
+  std::vector<DevBuf<float>> prop_rays_;  // per level < L - 1, [max_rays]: c_r L_r^l (allocated with the option)
   DevBuf<float> o_, d_, radii_, nears_, fars_, lm_, pix_;
   std::vector<DevBuf<float>> t_, w_, C_, dsig_, drgb_, loss_rays_, acc_, dist_;
-  // stop_level_grad = 0 (allocated only then): q^l = dL/dw^l [n][S] (levels < L - 1); for levels >= 1 the
-  // integrator's and the bin edges' dL/dt^l and their sum with the encoding's [n][S + 1]
+  // the interlevel loss of level l < L - 1 against the last level's (t, w): k_interlevel into q_[l] (accumulate: on
+  // top of the resampler adjoint's q^l) and prop_rays_[l]
+  void launch_interlevel_level(int n, int l, const float* lm, float msum, int accumulate);
+  void run_interlevel(int n, const float* d, const float* nears, const float* fars, const float* lm, const float* pix,
+                      float msum, nof_output_grad_fn cb, void* user);
+  // stop_level_grad = 0 (allocated only then; q_ also when the interlevel loss is first switched on): q^l =
+  // dL/dw^l [n][S] (levels < L - 1); for levels >= 1 the integrator's and the bin edges' dL/dt^l and their sum
+  // with the encoding's [n][S + 1]
   bool cross_ = false;
   std::vector<DevBuf<float>> q_, dtr_, dtb_, dt_;
   float* const* run_cross(int n, const float* o, const float* d, const float* radii, const float* nears,

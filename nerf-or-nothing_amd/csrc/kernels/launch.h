@@ -144,6 +144,19 @@ struct SamplePdfGradArgs {
 };
 hipError_t launch_sample_pdf_grad(const SamplePdfGradArgs& a, hipStream_t st);
 
+// ---- interlevel.hip: the interlevel (proposal) loss of one coarser level (nof_mipnerf_set_interlevel_loss) ----
+// w_grad [n][S_prop] (accumulate: added to, else overwritten) = dL/dw^ of mult lossmult[r] / msum L_r, L_r the
+// envelope loss of the proposal (t_prop [n][S_prop + 1], w_prop [n][S_prop]) against the target (t_tgt
+// [n][S_tgt + 1], w_tgt [n][S_tgt], a constant); rays ([n], optional) receives the per-ray term.  S_prop, S_tgt in
+// {64, 128, 256, 512} independently.
+struct InterlevelArgs {
+  int n, S_prop, S_tgt, accumulate;
+  const float *t_prop, *w_prop, *t_tgt, *w_tgt, *lossmult;
+  float msum, mult;
+  float *w_grad, *rays;
+};
+hipError_t launch_interlevel(const InterlevelArgs& a, hipStream_t st);
+
 // ---- raygrad.hip: one level's share of dL/d(origin), dL/d(direction) per ray (nof_mipnerf_set_ray_grad) ------
 // o_grad / d_grad [n][3] (accumulate: added to, else overwritten) from enc / denc [n S][P] (as EncodeGradArgs), the
 // level's sigma / dsigma [n S] (the integrator's |d|) and, ddir != null, the view encoding enc_dir / ddir [n][Vd]

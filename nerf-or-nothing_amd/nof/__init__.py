@@ -25,6 +25,7 @@ from .api import (  # noqa: F401
     grad_bucket_spans,
     image_metrics,
     kernel_gemm_h,
+    kernel_interlevel,
     learning_rate_decay,
     multiscale_layout,
     to_numpy,

@@ -151,6 +151,8 @@ SIGNATURES = {
     "nof_mipnerf_ray_grad": [P, C.POINTER(P), C.POINTER(P)],
     "nof_mipnerf_loss": [P, C.POINTER(F)],
     "nof_mipnerf_distortion_loss": [P, C.POINTER(F)],
+    "nof_mipnerf_set_interlevel_loss": [P, F],
+    "nof_mipnerf_interlevel_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],
     "nof_device_checks_selftest": [],
@@ -240,6 +242,7 @@ SIGNATURES = {
     "nof_kernel_render_grad": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P],
     "nof_kernel_render_grad_ex": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P],
     "nof_kernel_render_grad_dist": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P, P, P, P, I32, F, P, P],
+    "nof_kernel_interlevel": [I32, I32, P, P, I32, P, P, P, F, F, I32, P, P, P],
     "nof_kernel_sample_pdf_grad": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P, P],
     "nof_kernel_encode_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P],
     "nof_kernel_ray_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P],

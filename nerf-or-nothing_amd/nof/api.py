@@ -87,6 +87,15 @@ def kernel_gemm_h(stream=None, **fields) -> None:
     call("nof_kernel_gemm_h", C.byref(a), stream)
 
 
+def kernel_interlevel(n, samples_prop, t_prop, w_prop, samples_tgt, t_tgt, w_tgt, loss_mults, loss_mult_sum, mult,
+                      w_grad, rays=None, accumulate=False, stream=None) -> None:
+    """One k_interlevel launch (include/nof.h nof_kernel_interlevel): device pointers or tensors; w_grad
+    [n, samples_prop] is overwritten, or added to with accumulate; rays ([n], optional) receives the per-ray term."""
+    call("nof_kernel_interlevel", int(n), int(samples_prop), _ptr(t_prop), _ptr(w_prop), int(samples_tgt),
+         _ptr(t_tgt), _ptr(w_tgt), _ptr(loss_mults), float(loss_mult_sum), float(mult), int(bool(accumulate)),
+         _ptr(w_grad), _ptr(rays) or None, stream)
+
+
 class AcceleratedMLP:
     """Borrowed view of the MLP owned by an AcceleratedMipNeRF (AcceleratedMLP.h:7-45)."""
 
@@ -335,7 +344,8 @@ class AcceleratedMipNeRF:
     def cross_numpy(self, level: int) -> dict:
         """stop_level_grad = 0: the last step's cross-level terms of `level` (include/nof.h
         nof_mipnerf_cross_view): "w_grad" [n, S] = dL/dw from the next level's resampler, "t_grad" [n, S + 1] =
-        dL/dt; None where the level has none (the last level / level 0, or stop_level_grad = 1)."""
+        dL/dt; None where the level has none (the last level / level 0, or stop_level_grad = 1).  With
+        set_interlevel_loss(mult > 0) "w_grad" also holds that loss's dL/dw, at either stop_level_grad."""
         v = L.nof_level_view()
         call("nof_mipnerf_level_view", self._h, level, C.byref(v))
         q, dt = C.c_void_p(), C.c_void_p()
@@ -365,6 +375,19 @@ class AcceleratedMipNeRF:
         loss() stays the photometric loss."""
         out = C.c_float()
         call("nof_mipnerf_distortion_loss", self._h, C.byref(out))
+        return out.value
+
+    def set_interlevel_loss(self, mult: float) -> None:
+        """The interlevel (proposal) loss of mip-NeRF 360 times `mult` on every level but the last, whose (t, w) is
+        the stop-gradient target (include/nof.h nof_mipnerf_set_interlevel_loss); 0 switches it off.  Every
+        precision mode and both settings of stop_level_grad."""
+        call("nof_mipnerf_set_interlevel_loss", self._h, float(mult))
+
+    def interlevel_loss(self) -> float:
+        """The interlevel term of the last gradient step, summed over the coarser levels and the rays; 0.0 with the
+        option off.  loss() stays the photometric loss."""
+        out = C.c_float()
+        call("nof_mipnerf_interlevel_loss", self._h, C.byref(out))
         return out.value
 
     def numeric_status(self, clear: bool = True) -> int:

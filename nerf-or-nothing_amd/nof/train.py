@@ -32,7 +32,7 @@ class Trainer:
                  stream=None, print_every: int = 100, save_every: int = 0, ckpt_dir: str | None = None,
                  sync_check_every: int = 0, lr_init=5e-4, lr_final=5e-6, max_steps=1000000, lr_delay_steps=2500, lr_delay_mult=0.01,
                  grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
-                 stats: bool = False, refine_poses: float = 0.0, **config):
+                 stats: bool = False, refine_poses: float = 0.0, interlevel_loss_mult: float = 0.0, **config):
         import torch.distributed as dist
 
         self.dist = dist if dist.is_available() and dist.is_initialized() else None
@@ -60,6 +60,11 @@ class Trainer:
         self.device = device
         self.last_loss = None
         self.last_distortion = None  # the distortion term of the last print step (distortion_loss_mult > 0)
+        # the interlevel (proposal) loss: a setter, not a config field; every rank's model gets it
+        self.interlevel_loss_mult = float(interlevel_loss_mult)
+        self.last_interlevel = None  # its term of the last print step
+        if self.interlevel_loss_mult:
+            self.model.set_interlevel_loss(self.interlevel_loss_mult)
         # data parallel: the gradient arena is all-reduced bucket by bucket on a communication
         # stream ordered after the library's stream (self.stream, which may be any stream), and the
         # library's stream waits for the last bucket before Adam (nof.dp.BucketedAllReduce)
@@ -116,6 +121,9 @@ class Trainer:
             if self.cfg.distortion_loss_mult > 0:  # this rank's term, lambda_d sum mu L / sum mu (global sum mu)
                 self.last_distortion = self.model.distortion_loss()
                 line += f", Distortion: {self.last_distortion:.9g}"
+            if self.interlevel_loss_mult > 0:  # this rank's term as well (over the global sum mu: the ranks' add up)
+                self.last_interlevel = self.model.interlevel_loss()
+                line += f", Interlevel: {self.last_interlevel:.9g}"
             if self.with_stats:  # StatsUtil.cs:13,16-18, of the all-reduced gradient (identical on every rank)
                 self.last_stats = st = self.adam.stats()
                 line += (f", grad_norm: {st['grad_norm']:.9g}, grad_abs_max: {st['grad_abs_max']:.9g}, "
@@ -326,6 +334,10 @@ def parse_args(argv=None):
     ap.add_argument("--distortion-loss-mult", type=float, default=0.0, metavar="X",
                     help="the distortion loss of mip-NeRF 360 on the last level's weights, times X (0 = off; every "
                          "precision; with --no-stop-level-grad it also trains the coarse pass); printed next to the loss")
+    ap.add_argument("--interlevel-loss-mult", type=float, default=0.0, metavar="X",
+                    help="the interlevel (proposal) loss of mip-NeRF 360, times X: every coarser level's weights are "
+                         "pushed to be an upper envelope of the last level's (0 = off; every precision, with or "
+                         "without --no-stop-level-grad); printed next to the loss")
     # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70; 0 = off) and the step statistics
     ap.add_argument("--grad-max-norm", type=float, default=0.0, help="clip the gradient's global norm")
     ap.add_argument("--grad-max-val", type=float, default=0.0, help="clip every gradient element to +-this")
@@ -351,6 +363,8 @@ def parse_args(argv=None):
         ap.error("--refine-poses takes a learning rate > 0")
     if not (a.distortion_loss_mult >= 0 and a.distortion_loss_mult < float("inf")):
         ap.error("--distortion-loss-mult must be a finite number >= 0")
+    if not (a.interlevel_loss_mult >= 0 and a.interlevel_loss_mult < float("inf")):
+        ap.error("--interlevel-loss-mult must be a finite number >= 0")
     if a.refine_poses and not a.scene:
         ap.error("--refine-poses needs --scene: only a scene of poses and images has poses to refine")
     if a.holdout < 0 or a.holdout == 1:
@@ -385,7 +399,8 @@ def main(argv=None):
         tr = Trainer(ds, batch_size=a.batch, device=a.device, print_every=a.print_every, save_every=a.save_every,
                      ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
                      grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
-                     stats=a.stats, refine_poses=a.refine_poses, lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
+                     stats=a.stats, refine_poses=a.refine_poses, interlevel_loss_mult=a.interlevel_loss_mult,
+                     lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
                      precision=PRECISION_NAMES[a.precision], **net)
     except NofError as e:
         if a.refine_poses and e.status == 5:  # NOF_ERR_UNSUPPORTED: the library says what --refine-poses needs
