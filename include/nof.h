@@ -271,6 +271,21 @@ nof_status nof_mipnerf_set_interlevel_loss(nof_mipnerf* h, float mult);
 /* its term of the last gradient step, summed on the host in level order, then ray order (synchronises); 0 with the
  * option off; NOF_ERR_INVALID_ARG before a step.  nof_mipnerf_loss stays the photometric loss. */
 nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out);
+/* Scene contraction for unbounded scenes (mip-NeRF 360's; no counterpart in the reference).  With
+ * NOF_CONTRACT_SPHERE every sample's Gaussian (mean m, diagonal covariance v, as the cast makes them in world
+ * coordinates) is mapped into the ball of radius 2 before it is encoded: |m| <= 1 (and NaN) untouched, else
+ *   m' = (2 - 1 / n) m / n,  v' = diag(J diag(v) J^T),  J = a (I - u u^T) + b u u^T,
+ * n = |m|, u = m / n, a = (2 n - 1) / n^2, b = 1 / n^2 (the linearised covariance, kept diagonal as the IPE is).
+ * It applies wherever the object casts rays itself: the training step through both gradient entries,
+ * nof_mipnerf_render_device and nof_dataset_render_view, and to the adjoints of stop_level_grad = 0 and
+ * nof_mipnerf_set_ray_grad.  nof_mlp_get_output takes caller-encoded inputs and is unaffected.  Cameras are expected
+ * inside the unit ball; lindisp = 1 with a large far plane goes with it.  A hyper-parameter, not state: checkpoints
+ * do not hold it; it takes effect from the next call and allocates nothing (nof_config is not extended: the option
+ * is this setter).  Any-shape objects only (as nof_mipnerf_set_ray_grad); a fused 8x256 object: NOF_ERR_UNSUPPORTED,
+ * the object staying usable (NOF_CONTRACT_NONE is accepted there).  An unknown mode: NOF_ERR_INVALID_ARG. */
+enum { NOF_CONTRACT_NONE = 0, NOF_CONTRACT_SPHERE = 1 };
+nof_status nof_mipnerf_set_contraction(nof_mipnerf* h, int32_t mode);
+nof_status nof_mipnerf_get_contraction(nof_mipnerf* h, int32_t* mode);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
  * stated limit: an overflow surfaces here instead of silently): NOF_NUMERIC_FORWARD = a training
  * forward produced a non-finite composite colour; NOF_NUMERIC_DELTA = the f16x2 delta scaling saw a
@@ -731,6 +746,24 @@ nof_status nof_kernel_ray_grad(int32_t n, int32_t samples, const float* t, const
                                const float* sigma_grad, int32_t deg_view, const float* dev_enc_dir,
                                const float* dev_enc_dir_grad, int32_t accumulate, float* dev_o_grad,
                                float* dev_d_grad, void* stream);
+/* The scene contraction (nof_mipnerf_set_contraction) at the kernel entry points, for parity tests: the argument
+ * lists above plus a trailing contraction mode.  NOF_CONTRACT_SPHERE: nof_kernel_cast_contract stores the contracted
+ * Gaussians (k_cast_contract), and the two adjoints take dev_enc_pos as the encoding of the contracted Gaussians and
+ * apply the map's adjoint at the uncontracted ones.  NOF_CONTRACT_NONE: each is the entry point it extends, bit for
+ * bit. */
+nof_status nof_kernel_cast_contract(int32_t n, int32_t samples, const float* t, const float* origins,
+                                    const float* dirs, const float* radii, float* means, float* covs, void* stream,
+                                    int32_t ray_shape, int32_t contraction);
+nof_status nof_kernel_encode_grad_ex(int32_t n, int32_t samples, const float* t, const float* origins,
+                                     const float* dirs, const float* radii, int32_t ray_shape, int32_t min_deg,
+                                     int32_t max_deg, const float* dev_enc_pos, const float* dev_enc_pos_grad,
+                                     float* dev_t_grad, void* stream, int32_t contraction);
+nof_status nof_kernel_ray_grad_ex(int32_t n, int32_t samples, const float* t, const float* origins, const float* dirs,
+                                  const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                                  const float* dev_enc_pos, const float* dev_enc_pos_grad, const float* sigma,
+                                  const float* sigma_grad, int32_t deg_view, const float* dev_enc_dir,
+                                  const float* dev_enc_dir_grad, int32_t accumulate, float* dev_o_grad,
+                                  float* dev_d_grad, void* stream, int32_t contraction);
 nof_status nof_kernel_adam(int64_t n, float* params, const float* grads, float* m, float* v, float lr,
                            int32_t iteration, void* stream);
 

@@ -70,6 +70,7 @@ struct Args {
   bool no_stop_level_grad = false;  // MipNerfModel.StopLevelGrad = false (MipNerfModel.cs:13)
   float distortion_loss_mult = 0.0f;  // nof_config.distortion_loss_mult (0 = off)
   float interlevel_loss_mult = 0.0f;  // nof_mipnerf_set_interlevel_loss (0 = off)
+  bool contract = false;              // nof_mipnerf_set_contraction(NOF_CONTRACT_SPHERE)
   // Config (TrainState.cs:54-58)
   float lr_init = 5e-4f, lr_final = 5e-6f, lr_delay_mult = 0.01f;
   int max_steps = 1000000, lr_delay_steps = 2500;
@@ -89,7 +90,12 @@ struct Args {
                "--samples 64,64)\n"
                "                 [--lindisp] [--cylinder] [--density-bias B] [--rgb-padding P]\n"
                "                 [--no-stop-level-grad] [--distortion-loss-mult X] [--interlevel-loss-mult X]\n"
-               "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n");
+               "                 [--grad-max-norm N] [--grad-max-val V] [--weight-decay W] [--stats]\n"
+               "                 [--contract]  scene contraction for unbounded scenes (mip-NeRF 360): every sample's\n"
+               "                               Gaussian is mapped into the ball of radius 2 before it is encoded.  Cameras\n"
+               "                               are expected inside the unit ball; --lindisp with a large far plane goes\n"
+               "                               with it.  Needs the any-shape path: any other network than 8x256 in f32 or\n"
+               "                               f16p; the reference network in f16p, or f32 with --no-stop-level-grad\n");
   std::exit(code);
 }
 
@@ -124,6 +130,7 @@ Args parse(int argc, char** argv) {
     else if (k == "--no-stop-level-grad") a.no_stop_level_grad = true;
     else if (k == "--distortion-loss-mult") a.distortion_loss_mult = std::strtof(val(), nullptr);
     else if (k == "--interlevel-loss-mult") a.interlevel_loss_mult = std::strtof(val(), nullptr);
+    else if (k == "--contract") a.contract = true;
     else if (k == "--grad-max-norm") a.grad_max_norm = std::strtof(val(), nullptr);
     else if (k == "--grad-max-val") a.grad_max_val = std::strtof(val(), nullptr);
     else if (k == "--weight-decay") a.weight_decay = std::strtof(val(), nullptr);
@@ -284,6 +291,8 @@ int main(int argc, char** argv) {
     R.cfg.grad_buckets = G > 1 ? 1 : 0;
     CHECK(nof_mipnerf_create(&R.cfg, &R.model));
     if (a.interlevel_loss_mult > 0.0f) CHECK(nof_mipnerf_set_interlevel_loss(R.model, a.interlevel_loss_mult));
+    // refused here, before training, with the library's message, by a fused 8x256 precision
+    if (a.contract) CHECK(nof_mipnerf_set_contraction(R.model, NOF_CONTRACT_SPHERE));
     int32_t sizes[64], nsizes = 0;
     CHECK(nof_mipnerf_layer_sizes(R.model, sizes, 64, &nsizes));
     CHECK(nof_adam_create(sizes, nsizes, &R.cfg, &R.adam));

@@ -257,6 +257,15 @@ nof_status nof_mipnerf_set_interlevel_loss(nof_mipnerf* h, float mult) {
 nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out) {
   return guard([&] { ARG(h && out); DEV(h); *out = h->impl->interlevel_loss(); });
 }
+nof_status nof_mipnerf_set_contraction(nof_mipnerf* h, int32_t mode) {
+  return guard([&] {
+    ARG(h && (mode == NOF_CONTRACT_NONE || mode == NOF_CONTRACT_SPHERE));
+    h->impl->set_contraction(mode);
+  });
+}
+nof_status nof_mipnerf_get_contraction(nof_mipnerf* h, int32_t* mode) {
+  return guard([&] { ARG(h && mode); *mode = h->impl->contraction(); });
+}
 nof_status nof_mipnerf_render_device(nof_mipnerf* h, int32_t n, const float* o, const float* d, const float* radii,
                                      const float* nears, const float* fars, int32_t randomized, int32_t white_bkgd,
                                      nof_render_out* out) {
@@ -721,13 +730,19 @@ nof_status nof_kernel_sample_pdf(int32_t n, int32_t S_in, const float* t_in, con
                                    (hipStream_t)stream));
   });
 }
-nof_status nof_kernel_cast_ex(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* r,
-                              float* mean, float* cov, void* stream, int32_t ray_shape) {
+nof_status nof_kernel_cast_contract(int32_t n, int32_t S, const float* t, const float* o, const float* d,
+                                    const float* r, float* mean, float* cov, void* stream, int32_t ray_shape,
+                                    int32_t contraction) {
   return guard([&] {
     ARG(n >= 0 && S > 0 && t && o && d && r && mean && cov &&
         (ray_shape == NOF_RAY_CONICAL || ray_shape == NOF_RAY_CYLINDRICAL));
-    NOF_HIP(nof::launch_cast(n, S, t, o, d, r, mean, cov, (hipStream_t)stream, ray_shape));
+    ARG(contraction == NOF_CONTRACT_NONE || contraction == NOF_CONTRACT_SPHERE);
+    NOF_HIP(nof::launch_cast(n, S, t, o, d, r, mean, cov, (hipStream_t)stream, ray_shape, contraction));
   });
+}
+nof_status nof_kernel_cast_ex(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* r,
+                              float* mean, float* cov, void* stream, int32_t ray_shape) {
+  return nof_kernel_cast_contract(n, S, t, o, d, r, mean, cov, stream, ray_shape, NOF_CONTRACT_NONE);
 }
 nof_status nof_kernel_cast(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* r,
                            float* mean, float* cov, void* stream) {
@@ -829,10 +844,12 @@ nof_status nof_kernel_sample_pdf_grad(int32_t n, int32_t S_in, const float* t_in
     NOF_HIP(nof::launch_sample_pdf_grad(a, (hipStream_t)stream));
   });
 }
-nof_status nof_kernel_encode_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d,
-                                  const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
-                                  const float* enc, const float* denc, float* t_grad, void* stream) {
+nof_status nof_kernel_encode_grad_ex(int32_t n, int32_t S, const float* t, const float* o, const float* d,
+                                     const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                                     const float* enc, const float* denc, float* t_grad, void* stream,
+                                     int32_t contraction) {
   return guard([&] {
+    ARG(contraction == NOF_CONTRACT_NONE || contraction == NOF_CONTRACT_SPHERE);
     ARG(n >= 0 && S >= 64 && S <= 512 && S % 64 == 0 && t && o && d && radii && enc && denc && t_grad);
     ARG((ray_shape == NOF_RAY_CONICAL || ray_shape == NOF_RAY_CYLINDRICAL) && min_deg >= 0 && max_deg > min_deg &&
         max_deg <= 24);
@@ -840,15 +857,23 @@ nof_status nof_kernel_encode_grad(int32_t n, int32_t S, const float* t, const fl
     a.n = n; a.S = S; a.P = 6 * (max_deg - min_deg); a.min_deg = min_deg;
     a.cylinder = ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
     a.t = t; a.o = o; a.d = d; a.radius = radii; a.enc = enc; a.denc = denc; a.t_grad = t_grad;
+    a.contract = contraction != NOF_CONTRACT_NONE ? 1 : 0;
     NOF_HIP(nof::launch_encode_grad(a, (hipStream_t)stream));
   });
 }
-nof_status nof_kernel_ray_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* radii,
-                               int32_t ray_shape, int32_t min_deg, int32_t max_deg, const float* enc,
-                               const float* denc, const float* sigma, const float* dsigma, int32_t deg_view,
-                               const float* enc_dir, const float* ddir, int32_t accumulate, float* o_grad,
-                               float* d_grad, void* stream) {
+nof_status nof_kernel_encode_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d,
+                                  const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                                  const float* enc, const float* denc, float* t_grad, void* stream) {
+  return nof_kernel_encode_grad_ex(n, S, t, o, d, radii, ray_shape, min_deg, max_deg, enc, denc, t_grad, stream,
+                                   NOF_CONTRACT_NONE);
+}
+nof_status nof_kernel_ray_grad_ex(int32_t n, int32_t S, const float* t, const float* o, const float* d,
+                                  const float* radii, int32_t ray_shape, int32_t min_deg, int32_t max_deg,
+                                  const float* enc, const float* denc, const float* sigma, const float* dsigma,
+                                  int32_t deg_view, const float* enc_dir, const float* ddir, int32_t accumulate,
+                                  float* o_grad, float* d_grad, void* stream, int32_t contraction) {
   return guard([&] {
+    ARG(contraction == NOF_CONTRACT_NONE || contraction == NOF_CONTRACT_SPHERE);
     ARG(n >= 0 && S >= 32 && S <= 512 && S % 32 == 0 && t && o && d && radii && enc && denc && sigma && dsigma &&
         o_grad && d_grad);
     ARG((ray_shape == NOF_RAY_CONICAL || ray_shape == NOF_RAY_CYLINDRICAL) && min_deg >= 0 && max_deg > min_deg &&
@@ -860,8 +885,17 @@ nof_status nof_kernel_ray_grad(int32_t n, int32_t S, const float* t, const float
     a.Vd = 3 + 6 * deg_view; a.accumulate = accumulate ? 1 : 0;
     a.t = t; a.o = o; a.d = d; a.radius = radii; a.enc = enc; a.denc = denc; a.sigma = sigma; a.dsigma = dsigma;
     a.enc_dir = enc_dir; a.ddir = ddir; a.o_grad = o_grad; a.d_grad = d_grad;
+    a.contract = contraction != NOF_CONTRACT_NONE ? 1 : 0;
     NOF_HIP(nof::launch_ray_grad(a, (hipStream_t)stream));
   });
+}
+nof_status nof_kernel_ray_grad(int32_t n, int32_t S, const float* t, const float* o, const float* d, const float* radii,
+                               int32_t ray_shape, int32_t min_deg, int32_t max_deg, const float* enc,
+                               const float* denc, const float* sigma, const float* dsigma, int32_t deg_view,
+                               const float* enc_dir, const float* ddir, int32_t accumulate, float* o_grad,
+                               float* d_grad, void* stream) {
+  return nof_kernel_ray_grad_ex(n, S, t, o, d, radii, ray_shape, min_deg, max_deg, enc, denc, sigma, dsigma, deg_view,
+                                enc_dir, ddir, accumulate, o_grad, d_grad, stream, NOF_CONTRACT_NONE);
 }
 nof_status nof_kernel_adam(int64_t n, float* p, const float* g, float* m, float* v, float lr, int32_t it,
                            void* stream) {

@@ -299,7 +299,8 @@ void AcceleratedMLP::forward_fused(int level, int n, int samples, const float* t
     NOF_REQUIRE(n <= cfg_.max_rays, "n_rays exceeds max_rays");
     GenLevel& G = gl_[level];
     tb(kTMlpFwd);
-    NOF_HIP(nof::launch_cast(n, samples, t, origins, dirs, radii, G.mean.p, G.cov.p, st_, cfg_.ray_shape));
+    NOF_HIP(nof::launch_cast(n, samples, t, origins, dirs, radii, G.mean.p, G.cov.p, st_, cfg_.ray_shape,
+                             contraction_));
     int v;
     NOF_HIP(nof::launch_encode_g(n, samples, G.mean.p, G.cov.p, dirs, gmin_deg_, gP_, gVd_, G.enc_pos.p, G.enc_dir.p,
                                  st_, &v));
@@ -933,6 +934,15 @@ void AcceleratedMLP::set_ray_grad(bool on) {
   rg_job_ = RayGradJob();
 }
 
+void AcceleratedMLP::set_contraction(int mode) {
+  NOF_REQUIRE(mode == NOF_CONTRACT_NONE || mode == NOF_CONTRACT_SPHERE, "unknown contraction mode");
+  if (mode != NOF_CONTRACT_NONE && !generic_)
+    throw Error(NOF_ERR_UNSUPPORTED,
+                "scene contraction needs the any-shape path: the fused 8x256 kernels encode in world coordinates "
+                "(use NOF_PRECISION_F16_PRODUCTS, or NOF_PRECISION_F32 with stop_level_grad = 0)");
+  contraction_ = mode;
+}
+
 void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t ldz, int nout, nof::GemmSrc x,
                                int ncols, int M, int accumulate, float* bias_dst, const uint32_t* scale) {
   int ks, kc;
@@ -1198,6 +1208,7 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     nof::RayGradArgs ra{};
     ra.n = L.n; ra.S = S; ra.P = P; ra.min_deg = gmin_deg_; ra.Vd = Vd;
     ra.cylinder = cfg_.ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    ra.contract = contraction_ != NOF_CONTRACT_NONE ? 1 : 0;
     ra.accumulate = rg_job_.first ? 0 : 1;
     ra.t = rg_job_.t[level]; ra.o = rg_job_.o; ra.d = rg_job_.d; ra.radius = rg_job_.radius;
     ra.enc = G.ep; ra.denc = gdenc_.p; ra.sigma = L.sigma.p; ra.dsigma = density_grad;
@@ -1514,6 +1525,7 @@ float* const* AcceleratedMipNeRF::run_cross(int n, const float* o, const float* 
     nof::EncodeGradArgs ea{};
     ea.n = n; ea.S = S; ea.P = 6 * (cfg_.max_deg_point - cfg_.min_deg_point); ea.min_deg = cfg_.min_deg_point;
     ea.cylinder = cfg_.ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
+    ea.contract = mlp->contraction() != NOF_CONTRACT_NONE ? 1 : 0;
     ea.t = t_[lv].p; ea.o = o; ea.d = d; ea.radius = radii; ea.enc = mlp->enc_pos(lv); ea.denc = denc;
     ea.add0 = dtr_[lv].p; ea.add1 = lv + 1 < L ? dtb_[lv].p : nullptr;
     ea.t_grad = dt_[lv].p;

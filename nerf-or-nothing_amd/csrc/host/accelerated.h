@@ -189,6 +189,12 @@ class AcceleratedMLP {
   void set_ray_grad_job(const RayGradJob* job) { rg_job_ = job ? *job : RayGradJob(); }
   const float* ray_o_grad() const { return rg_o_.p; }
   const float* ray_d_grad() const { return rg_d_.p; }
+  // Scene contraction (include/nof.h nof_mipnerf_set_contraction; any-shape path only, else
+  // NOF_ERR_UNSUPPORTED): NOF_CONTRACT_SPHERE maps every Gaussian this object casts into the ball of radius 2 before
+  // it is encoded (forward_fused's cast), and the level's k_ray_grad / the owner's k_encode_grad take the map's
+  // adjoint.  A hyper-parameter: nothing is allocated, it holds from the next call on.
+  void set_contraction(int mode);
+  int contraction() const { return contraction_; }
 
  private:
   struct Schedule {
@@ -273,6 +279,7 @@ class AcceleratedMLP {
   DevBuf<float> gd2_, gdenc_, gdenc_part_;
   void denc_alloc(int first_level);  // those three, for levels >= first_level (grown, never shrunk)
   bool ray_grad_ = false;
+  int contraction_ = NOF_CONTRACT_NONE;
   RayGradJob rg_job_;
   DevBuf<float> gddir_, rg_o_, rg_d_;  // dL/d(view PE) [rays][Vd]; dL/do, dL/dd [rays][3]
   // non-null: gen_backward launches nothing and gen_wgrad records its split-K slab need here instead (the
@@ -343,6 +350,10 @@ class AcceleratedMipNeRF {
   // its term of the last gradient step, summed on the host in level order, then ray order (0 with the option off;
   // synchronises)
   float interlevel_loss();
+  // Scene contraction (include/nof.h nof_mipnerf_set_contraction): the mode of every cast this object
+  // makes from the next call on (training step, Render, the dataset's render_view) and of their adjoints
+  void set_contraction(int mode) { mlp->set_contraction(mode); }
+  int contraction() const { return mlp->contraction(); }
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
   // per level comp_rgb [n][3], distance [n], acc [n] (device, borrowed until the next call).

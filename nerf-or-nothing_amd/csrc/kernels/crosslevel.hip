@@ -8,6 +8,7 @@
 //   * (the integrator's dL/dt lives with the integrator: render.hip k_render_bwd_x).
 // No float atomics: every sum runs in a fixed order, the results are bit-identical run to run.
 #include "common.h"
+#include "contract.h"
 #include "geometry.h"
 #include "launch.h"
 #include "resample.h"
@@ -56,6 +57,7 @@ constexpr int kEgThreads = 256; // 8 threads per staged sample
 // S P floats start 16-byte aligned, S being a multiple of 64) go to LDS by 16-byte coalesced loads; 8 threads
 // per sample then take the degrees q, q + 8, ... and a fixed butterfly adds their partial sums.  Feature order:
 // the any-shape encoder's (generic.hip k_encode_g): 6 f + j = sin, 6 f + 3 + j = "cos" at degree min_deg + f.
+template <bool CONTRACT>
 __global__ __launch_bounds__(kEgThreads) void k_encode_grad(EncodeGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int S = a.S, P = a.P, ndeg = P / 6;
@@ -91,6 +93,14 @@ __global__ __launch_bounds__(kEgThreads) void k_encode_grad(EncodeGradArgs a) {
     //   d(damp sin y) / dy = f_c + kappa f_s,   d(damp sin(y + pi / 2 + kappa)) / dy = -f_s - kappa f_c
     float mu[3], cv[3];
     frustum_gaussian(tr[c0 + ls], tr[c0 + ls + 1], oo, dv, radius, mu, cv, a.cylinder != 0);
+    // CONTRACT: the stored features were evaluated at the contracted mean (kappa's y); the map's adjoint below is
+    // taken at the uncontracted Gaussian
+    float m0[3], v0[3];
+    if constexpr (CONTRACT) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { m0[j] = mu[j]; v0[j] = cv[j]; }
+      contract_gaussian(mu, cv);
+    }
     for (int f = q; f < ndeg; f += 8) {
       const float s = (float)(1u << (a.min_deg + f));  // (degrees <= 24)
       const float hs2 = -0.5f * s * s;
@@ -120,6 +130,7 @@ __global__ __launch_bounds__(kEgThreads) void k_encode_grad(EncodeGradArgs a) {
     }
     if (q == 0) {
       const int k = c0 + ls;
+      if constexpr (CONTRACT) contract_adjoint(m0, v0, dm, dc);
       // mean_j = d_j tmean + o_j ; cov_j = tvar d_j^2 + rvar (1 - d_j^2 / |d|^2)
       const float dtmean = (dv[0] * dm[0] + dv[1] * dm[1]) + dv[2] * dm[2];
       const float dtvar = (dd[0] * dc[0] + dd[1] * dc[1]) + dd[2] * dc[2];
@@ -148,7 +159,10 @@ hipError_t launch_encode_grad(const EncodeGradArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
   const size_t shm = sizeof(float) * (2 * (size_t)kEgChunk * a.P + 2 * (size_t)a.S);
   if (shm > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_encode_grad, dim3(a.n), dim3(kEgThreads), shm, st, a);
+  if (a.contract)
+    hipLaunchKernelGGL(k_encode_grad<true>, dim3(a.n), dim3(kEgThreads), shm, st, a);
+  else
+    hipLaunchKernelGGL(k_encode_grad<false>, dim3(a.n), dim3(kEgThreads), shm, st, a);
   return hipGetLastError();
 }
 

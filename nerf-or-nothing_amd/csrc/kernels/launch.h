@@ -25,9 +25,10 @@ hipError_t launch_sample_stratified(int n, int S, const float* nears, const floa
 hipError_t launch_sample_pdf(int n, int S_in, const float* t_in, const float* w, int S_out, float padding,
                              int randomized, uint64_t seed, uint32_t step, uint32_t level, uint32_t ray_base,
                              float* t_out, int32_t* idx_out, hipStream_t st);
-// ray_shape 1: cylinders (CylinderToGaussian MH:403-409) instead of conical frustums
+// ray_shape 1: cylinders (CylinderToGaussian MH:403-409) instead of conical frustums; contraction != 0: the scene
+// contraction (contract.h) applied to every Gaussian before it is stored (k_cast_contract; 0: k_cast, as it was)
 hipError_t launch_cast(int n, int S, const float* t, const float* o, const float* d, const float* radius,
-                       float* mean, float* cov, hipStream_t st, int ray_shape = 0);
+                       float* mean, float* cov, hipStream_t st, int ray_shape = 0, int contraction = 0);
 hipError_t launch_encode(int n, int S, const float* mean, const float* cov, const float* d, float* enc_pos,
                          float* enc_dir, hipStream_t st);
 
@@ -123,11 +124,13 @@ hipError_t launch_render_bwd_x(const RenderBwdXArgs& a, hipStream_t st);
 // t_grad [n][S + 1] (overwritten) = (add0 +) d/dt of sum_{m, F} denc[m][F] enc[m][F](t) (+ add1): enc / denc
 // [n S][P], P = 6 degrees from min_deg in the any-shape encoder's feature order, enc the stored forward
 // encoding; add0 / add1 (optional, [n][S + 1]) are added before / after in that order.  S a multiple of 64.
+// contract != 0: enc is the encoding of the contracted Gaussians (contract.h; k_encode_grad<true>).
 struct EncodeGradArgs {
   int n, S, P, min_deg, cylinder;
   const float *t, *o, *d, *radius, *enc, *denc;
   const float *add0, *add1;
   float* t_grad;
+  int contract;
 };
 hipError_t launch_encode_grad(const EncodeGradArgs& a, hipStream_t st);
 // The adjoint of launch_sample_pdf (same sampling arguments): t_out_grad [n][S_out + 1] -> w_grad [n][S_in]
@@ -160,12 +163,14 @@ hipError_t launch_interlevel(const InterlevelArgs& a, hipStream_t st);
 // ---- raygrad.hip: one level's share of dL/d(origin), dL/d(direction) per ray (nof_mipnerf_set_ray_grad) ------
 // o_grad / d_grad [n][3] (accumulate: added to, else overwritten) from enc / denc [n S][P] (as EncodeGradArgs), the
 // level's sigma / dsigma [n S] (the integrator's |d|) and, ddir != null, the view encoding enc_dir / ddir [n][Vd]
-// (Vd = 3 + 6 deg_view, dir_feature's order).  S a multiple of 32, at most 512.
+// (Vd = 3 + 6 deg_view, dir_feature's order).  S a multiple of 32, at most 512.  contract != 0: as EncodeGradArgs
+// (k_ray_grad<true>).
 struct RayGradArgs {
   int n, S, P, min_deg, cylinder, Vd, accumulate;
   const float *t, *o, *d, *radius, *enc, *denc, *sigma, *dsigma;
   const float *enc_dir, *ddir;
   float *o_grad, *d_grad;
+  int contract;
 };
 hipError_t launch_ray_grad(const RayGradArgs& a, hipStream_t st);
 

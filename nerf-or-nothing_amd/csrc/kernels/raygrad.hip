@@ -9,6 +9,7 @@
 // the stored cos phase's rounding corrected to first order).  No float atomics: every sum runs in a fixed order, two
 // runs give the same bits.
 #include "common.h"
+#include "contract.h"
 #include "geometry.h"
 #include "launch.h"
 
@@ -43,6 +44,7 @@ __device__ __forceinline__ void frustum_moments(float t0, float t1, float radius
 // ... and a fixed butterfly adds their partial sums; the sample's 7 terms go to LDS.  Then 7 groups of 32 lanes sum
 // the S samples' terms (lane l: samples l, l + 32, ... in order, then a fixed butterfly), and three threads add the
 // integrator's |d| term and the view encoding's and write the ray's six floats.
+template <bool CONTRACT>
 __global__ __launch_bounds__(kRgThreads) void k_ray_grad(RayGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float s_sum[8];
@@ -76,6 +78,13 @@ __global__ __launch_bounds__(kRgThreads) void k_ray_grad(RayGradArgs a) {
     float mu[3], cv[3];
     const float t0 = tr[c0 + ls], t1 = tr[c0 + ls + 1];
     frustum_gaussian(t0, t1, oo, dv, radius, mu, cv, a.cylinder != 0);
+    // CONTRACT: kappa's y is the contracted mean's; the map's adjoint below is taken at the uncontracted Gaussian
+    float m0[3], v0[3];
+    if constexpr (CONTRACT) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { m0[j] = mu[j]; v0[j] = cv[j]; }
+      contract_gaussian(mu, cv);
+    }
     for (int f = q; f < ndeg; f += 8) {
       const float s = (float)(1u << (a.min_deg + f));  // (degrees <= 24)
       const float hs2 = -0.5f * s * s;
@@ -105,6 +114,7 @@ __global__ __launch_bounds__(kRgThreads) void k_ray_grad(RayGradArgs a) {
     }
     if (q == 0) {
       const int k = c0 + ls;
+      if constexpr (CONTRACT) contract_adjoint(m0, v0, dm, dc);
       float tmean, tvar, rvar;
       frustum_moments(t0, t1, radius, a.cylinder != 0, &tmean, &tvar, &rvar);
       // d mean_j / d d_j = tmean;  d cov_j / d d_j = 2 d_j (tvar - rvar / D);  d cov_i / d d_j (through D) =
@@ -163,7 +173,10 @@ hipError_t launch_ray_grad(const RayGradArgs& a, hipStream_t st) {
   if (a.ddir && (!a.enc_dir || a.Vd < 3 || (a.Vd - 3) % 6 != 0 || (a.Vd - 3) / 6 > 24)) return hipErrorInvalidValue;
   const size_t shm = sizeof(float) * (2 * (size_t)kRgChunk * a.P + (size_t)kRgTerms * a.S);
   if (shm > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_ray_grad, dim3(a.n), dim3(kRgThreads), shm, st, a);
+  if (a.contract)
+    hipLaunchKernelGGL(k_ray_grad<true>, dim3(a.n), dim3(kRgThreads), shm, st, a);
+  else
+    hipLaunchKernelGGL(k_ray_grad<false>, dim3(a.n), dim3(kRgThreads), shm, st, a);
   return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 // get_resampled_t_vals (AF:246-291; broken per D4) with the C# semantics
 // SampleAlongRay (MH:611-631) / ResampleAlongRay + SortedPiecewiseConstantPDF (MH:634-666, 774-851).
 #include "common.h"
+#include "contract.h"
 #include "geometry.h"
 #include "launch.h"
 #include "resample.h"
@@ -79,6 +80,23 @@ __global__ void k_cast(int n, int S, const float* __restrict__ t, const float* _
   for (int j = 0; j < 3; ++j) { mean[(size_t)gid * 3 + j] = mu[j]; cov[(size_t)gid * 3 + j] = cv[j]; }
 }
 
+// k_cast with the scene contraction (contract.h, nof_mipnerf_set_contraction) applied before the two 12-byte stores: no
+// extra pass over mean and cov.  A kernel of its own: k_cast is the launch it was.
+__global__ void k_cast_contract(int n, int S, const float* __restrict__ t, const float* __restrict__ o,
+                                const float* __restrict__ d, const float* __restrict__ radius, int cylinder,
+                                float* __restrict__ mean, float* __restrict__ cov) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= n * S) return;
+  const int r = gid / S;
+  const int k = gid - r * S;
+  const float oo[3] = {o[3 * r], o[3 * r + 1], o[3 * r + 2]};
+  const float dd[3] = {d[3 * r], d[3 * r + 1], d[3 * r + 2]};
+  float mu[3], cv[3];
+  frustum_gaussian(t[(size_t)r * (S + 1) + k], t[(size_t)r * (S + 1) + k + 1], oo, dd, radius[r], mu, cv, cylinder != 0);
+  contract_gaussian(mu, cv);
+  for (int j = 0; j < 3; ++j) { mean[(size_t)gid * 3 + j] = mu[j]; cov[(size_t)gid * 3 + j] = cv[j]; }
+}
+
 // encode_input_data (AF:187-221, D5 fixed): enc_pos [n*S][96] (reference feature order), enc_dir [n][27].
 __global__ void k_encode(int n, int S, const float* __restrict__ mean, const float* __restrict__ cov,
                          const float* __restrict__ d, float* __restrict__ enc_pos, float* __restrict__ enc_dir) {
@@ -120,10 +138,14 @@ hipError_t launch_sample_pdf(int n, int S_in, const float* t_in, const float* w,
 }
 
 hipError_t launch_cast(int n, int S, const float* t, const float* o, const float* d, const float* radius,
-                       float* mean, float* cov, hipStream_t st, int ray_shape) {
+                       float* mean, float* cov, hipStream_t st, int ray_shape, int contraction) {
   const int total = n * S;
   if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_cast, dim3((total + 255) / 256), dim3(256), 0, st, n, S, t, o, d, radius, ray_shape, mean, cov);
+  if (contraction)
+    hipLaunchKernelGGL(k_cast_contract, dim3((total + 255) / 256), dim3(256), 0, st, n, S, t, o, d, radius, ray_shape,
+                       mean, cov);
+  else
+    hipLaunchKernelGGL(k_cast, dim3((total + 255) / 256), dim3(256), 0, st, n, S, t, o, d, radius, ray_shape, mean, cov);
   return hipGetLastError();
 }
 

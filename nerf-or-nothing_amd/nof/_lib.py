@@ -152,6 +152,8 @@ SIGNATURES = {
     "nof_mipnerf_loss": [P, C.POINTER(F)],
     "nof_mipnerf_distortion_loss": [P, C.POINTER(F)],
     "nof_mipnerf_set_interlevel_loss": [P, F],
+    "nof_mipnerf_set_contraction": [P, I32],
+    "nof_mipnerf_get_contraction": [P, P],
     "nof_mipnerf_interlevel_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],
@@ -237,6 +239,7 @@ SIGNATURES = {
     "nof_kernel_sample_pdf": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P],
     "nof_kernel_cast": [I32, I32, P, P, P, P, P, P, P],
     "nof_kernel_cast_ex": [I32, I32, P, P, P, P, P, P, P, I32],
+    "nof_kernel_cast_contract": [I32, I32, P, P, P, P, P, P, P, I32, I32],
     "nof_kernel_encode": [I32, I32, P, P, P, P, P, P],
     "nof_kernel_render": [I32, I32, P, P, P, P, I32, P, P, P],
     "nof_kernel_render_grad": [I32, I32, P, P, P, P, I32, P, P, P, P, F, F, P, P, P],
@@ -246,6 +249,8 @@ SIGNATURES = {
     "nof_kernel_sample_pdf_grad": [I32, I32, P, P, I32, F, I32, U64, U32, U32, U32, P, P, P, P],
     "nof_kernel_encode_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P],
     "nof_kernel_ray_grad": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P],
+    "nof_kernel_encode_grad_ex": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32],
+    "nof_kernel_ray_grad_ex": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P, I32],
     "nof_kernel_adam": [C.c_int64, P, P, P, P, F, I32, P],
     "nof_kernel_gemm_h": [C.POINTER(nof_gemm_args), P],
 }

@@ -390,6 +390,20 @@ class AcceleratedMipNeRF:
         call("nof_mipnerf_interlevel_loss", self._h, C.byref(out))
         return out.value
 
+    def set_contraction(self, mode=1) -> None:
+        """Scene contraction for unbounded scenes (include/nof.h nof_mipnerf_set_contraction): 1 / True
+        (NOF_CONTRACT_SPHERE) maps every sample's Gaussian into the ball of radius 2 before it is encoded, in the
+        training step, render_device and RayDataset.render_view; 0 / False switches it off.  Cameras are expected
+        inside the unit ball.  A hyper-parameter (checkpoints do not hold it); any-shape path only: a fused 8x256
+        model raises NofError(NOF_ERR_UNSUPPORTED)."""
+        call("nof_mipnerf_set_contraction", self._h, int(mode))
+
+    def contraction(self) -> int:
+        """The contraction mode in force (0 = none, 1 = sphere)."""
+        out = C.c_int32()
+        call("nof_mipnerf_get_contraction", self._h, C.byref(out))
+        return out.value
+
     def numeric_status(self, clear: bool = True) -> int:
         """NOF_NUMERIC_* bits (non-finite forward outputs / output gradients) since the last clear."""
         out = C.c_uint32()

@@ -9,6 +9,8 @@ never implements.
                                                                 (every 8th view held out, rendered and scored)
     python -m nof.train --scene scene.npz --refine-poses 1e-3 --precision f16p
                                                                 (the scene's poses refined jointly with the field)
+    python -m nof.train --scene scene.npz --contract --lindisp --precision f16p
+                                                                (an unbounded scene: space contracted into a ball)
 
 One step = dataset batch (device gather) -> AcceleratedMipNeRF.get_gradient_device (fused loss
 gradient) -> [all-reduce of the gradient arena when torch.distributed is initialised] ->
@@ -32,7 +34,8 @@ class Trainer:
                  stream=None, print_every: int = 100, save_every: int = 0, ckpt_dir: str | None = None,
                  sync_check_every: int = 0, lr_init=5e-4, lr_final=5e-6, max_steps=1000000, lr_delay_steps=2500, lr_delay_mult=0.01,
                  grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
-                 stats: bool = False, refine_poses: float = 0.0, interlevel_loss_mult: float = 0.0, **config):
+                 stats: bool = False, refine_poses: float = 0.0, interlevel_loss_mult: float = 0.0,
+                 contract: bool = False, **config):
         import torch.distributed as dist
 
         self.dist = dist if dist.is_available() and dist.is_initialized() else None
@@ -65,6 +68,9 @@ class Trainer:
         self.last_interlevel = None  # its term of the last print step
         if self.interlevel_loss_mult:
             self.model.set_interlevel_loss(self.interlevel_loss_mult)
+        # scene contraction: a setter as well; refused here, before training, by a fused 8x256 precision
+        if contract:
+            self.model.set_contraction(1)
         # data parallel: the gradient arena is all-reduced bucket by bucket on a communication
         # stream ordered after the library's stream (self.stream, which may be any stream), and the
         # library's stream waits for the last bucket before Adam (nof.dp.BucketedAllReduce)
@@ -351,6 +357,11 @@ def parse_args(argv=None):
                          "per-view (rotation vector, translation); writes poses_refined.npy into --ckpt-dir (default: "
                          "the working directory).  Needs the any-shape path: any other network than 8x256 in f32 or "
                          "f16p; for the reference network --precision f16p, or f32 with --no-stop-level-grad")
+    ap.add_argument("--contract", action="store_true",
+                    help="scene contraction for unbounded scenes (mip-NeRF 360): every sample's Gaussian is mapped into "
+                         "the ball of radius 2 before it is encoded.  Cameras are expected inside the unit ball (scale the "
+                         "poses accordingly); --lindisp with a large far plane goes with it.  Needs the any-shape path, as "
+                         "--refine-poses does")
     # the test split (Config.LlffHold / GcEvery, TrainState.cs:53,63): held-out views rendered and scored on the device
     ap.add_argument("--holdout", type=int, default=0, metavar="N",
                     help="--scene: hold out every N-th view (i %% N == 0) as the test split; evaluated at the end")
@@ -400,11 +411,13 @@ def main(argv=None):
                      ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
                      grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
                      stats=a.stats, refine_poses=a.refine_poses, interlevel_loss_mult=a.interlevel_loss_mult,
-                     lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
+                     contract=a.contract, lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
                      precision=PRECISION_NAMES[a.precision], **net)
     except NofError as e:
         if a.refine_poses and e.status == 5:  # NOF_ERR_UNSUPPORTED: the library says what --refine-poses needs
             raise SystemExit(f"--refine-poses: {e}")
+        if a.contract and e.status == 5:
+            raise SystemExit(f"--contract: {e}")
         raise
     if a.resume:
         tr.resume(a.resume)
