@@ -286,6 +286,38 @@ nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out);
 enum { NOF_CONTRACT_NONE = 0, NOF_CONTRACT_SPHERE = 1 };
 nof_status nof_mipnerf_set_contraction(nof_mipnerf* h, int32_t mode);
 nof_status nof_mipnerf_get_contraction(nof_mipnerf* h, int32_t* mode);
+/* Per-view appearance embeddings (NeRF-W / mip-NeRF 360's GLO vectors; no counterpart in the reference; DESIGN.md
+ * 6j).  With appearance_views = V and appearance_dim = G > 0 the model owns a zero-initialised fp32 table E [V][G]
+ * outside the parameter arena, and the view layer (layer net_depth + 1) has in = W + Vd + G: its input for every
+ * sample of ray r is [h | viewPE(d_r) | E[view(r)]].  The parameter layout, the Glorot initialisation (fan-in = the
+ * widened in), nof_mipnerf_layer_sizes, Adam, checkpoints and the data-parallel arena see only a wider layer; the
+ * table is not in checkpoints.  Any-shape objects only: a fused 8x256 object (precision modes 0-4 with the reference
+ * shape and stop_level_grad = 1) with G > 0 is NOF_ERR_UNSUPPORTED.  ext == NULL or appearance_dim == 0 is exactly
+ * nof_mipnerf_create.  size = sizeof the caller's struct (the struct grows at its end).  NOF_ERR_INVALID_ARG, before
+ * any device call: dim < 0, dim > 256, dim > 0 with views <= 0, views * dim >= 2^31, size too small. */
+typedef struct nof_model_ext {
+  uint32_t size;
+  int32_t appearance_views, appearance_dim;
+} nof_model_ext;
+nof_status nof_mipnerf_create_ex(const nof_config* cfg, const nof_model_ext* ext, nof_mipnerf** out);
+/* Borrowed device pointers to E and to its gradient dE, each views x dim floats.  The caller owns the update: a
+ * second nof_adam created with layer_sizes = {views * dim} steps the table (and a data-parallel caller all-reduces
+ * dE itself, as the pose buffer).  dE[v][g] = sum over levels, then over the rays r of view v, of
+ * sum_o gray^l[r][o] W_view[o][W + Vd + g] (gray^l: the view layer's deltas summed over the ray's samples), formed
+ * by every step through either gradient entry in a fixed order (bitwise repeatable): overwritten, or added to with
+ * NOF_GRAD_ACCUMULATE; a view without a ray gets 0 (accumulating: stays as it is).  A model without appearance:
+ * NOF_ERR_INVALID_ARG. */
+nof_status nof_mipnerf_appearance(nof_mipnerf* h, float** dev_table, float** dev_grad, int32_t* views, int32_t* dim);
+/* The view ids [n] (device ints) of the rays of the NEXT single call that casts rays: either gradient entry, or
+ * nof_mipnerf_render_device.  They are read in that call's stream work; the call then resets the pointer to NULL.
+ * A ray whose id lies outside [0, views) reads the zero vector and contributes to no table row (lib/libnof_check.so
+ * sets NOF_CHECK_GATHER for it).  A gradient step on an appearance model with no ids set: NOF_ERR_INVALID_ARG ("ray
+ * views"), the object staying usable. */
+nof_status nof_mipnerf_set_ray_views(nof_mipnerf* h, const int32_t* dev_view_ids);
+/* The constant view of calls that have no per-ray ids: nof_mipnerf_render_device without ids,
+ * nof_dataset_render_view and nof_mlp_get_output.  -1 (the default): the zero vector.  Out of range:
+ * NOF_ERR_INVALID_ARG.  (nof_mlp_get_gradient leaves dE alone.) */
+nof_status nof_mipnerf_set_render_appearance(nof_mipnerf* h, int32_t view);
 /* Non-finite detection, every precision mode (the f16x2 perf mode's fp16 activation range is its
  * stated limit: an overflow surfaces here instead of silently): NOF_NUMERIC_FORWARD = a training
  * forward produced a non-finite composite colour; NOF_NUMERIC_DELTA = the f16x2 delta scaling saw a
@@ -469,7 +501,9 @@ nof_status nof_dp_init_loopback(int32_t k, int32_t device, nof_dp** out /* k han
  * sum; a shard runs as shard / micro_batch micro-batches (0 = one), the later ones accumulating;
  * the gradient arenas are all-reduced (bucket by bucket when the communicators are attached, else one
  * grouped all-reduce); every replica applies Adam(lr); then a bounded nof_dp_wait.  Replica
- * parameters stay bitwise identical.  *loss_mult_sum (optional) = the global sum. */
+ * parameters stay bitwise identical.  *loss_mult_sum (optional) = the global sum.  A model with appearance
+ * embeddings (nof_mipnerf_create_ex) is refused, NOF_ERR_UNSUPPORTED: the table's all-reduce and its Adam are the
+ * caller's, as the pose buffer's are. */
 nof_status nof_dp_train_step(int32_t n, nof_dp* const* dps, nof_mipnerf* const* models, nof_adam* const* adams,
                              nof_dataset* const* datasets, int32_t global_batch, int32_t micro_batch, uint64_t seed,
                              int32_t step, float lr, float* loss_mult_sum);
@@ -538,6 +572,10 @@ nof_status nof_dataset_render_view(nof_dataset* ds, nof_mipnerf* model, int32_t 
  * NOF_ERR_UNSUPPORTED: not image-backed, or an NDC scene (ConvertToNdc is not differentiated here). */
 nof_status nof_dataset_pose_grad(nof_dataset* ds, int32_t n, const float* dev_o_grad, const float* dev_d_grad,
                                  float* dev_pose_grad, int32_t accumulate, void* stream);
+/* The view of every ray of the dataset's LAST nof_dataset_next batch (its record_index decoded as
+ * nof_multiscale_layout orders the records) -> dev_view_ids [n], the ids nof_mipnerf_set_ray_views takes.
+ * Image-backed datasets only (else NOF_ERR_UNSUPPORTED); n larger than that batch: NOF_ERR_INVALID_ARG. */
+nof_status nof_dataset_batch_views(nof_dataset* ds, int32_t n, int32_t* dev_view_ids, void* stream);
 /* the image-backed dataset's pose table, V x 12 host floats.  set: ordered with the dataset's next gather and with
  * nof_dataset_render_view (it waits for the device, then copies); rays are made from the table inside the
  * gather, so nothing is regenerated. */
@@ -798,6 +836,16 @@ typedef struct nof_gemm_args {
   int32_t ksplit;
 } nof_gemm_args;
 nof_status nof_kernel_gemm_h(const nof_gemm_args* args, void* stream);
+/* The appearance embeddings' two kernels (appearance.hip), for parity tests.  gather: out [n][vd + dim]
+ * = [enc_dir [n][vd] row | table [views][dim] row ids[r]]; ids == NULL: row const_view for every ray; an id outside
+ * [0, views): zeros.  grad: d_table [views][dim] = per view, the sum of the rows of d_app [n][dim] whose id is that
+ * view, in a fixed order; accumulate = 0 overwrites (a view without a ray: exactly 0), 1 adds (such a view: left
+ * bitwise as it is).  dim in [1, 256]. */
+nof_status nof_kernel_appearance_gather(int32_t n, int32_t vd, int32_t dim, int32_t views, const float* enc_dir,
+                                        const float* table, const int32_t* ids, int32_t const_view, float* out,
+                                        void* stream);
+nof_status nof_kernel_appearance_grad(int32_t n, int32_t dim, int32_t views, const int32_t* ids, const float* d_app,
+                                      float* d_table, int32_t accumulate, void* stream);
 
 /* ---- per-kernel timing (hipEvents on the object's stream) ----------------------------------- */
 #define NOF_NUM_TIMERS 8

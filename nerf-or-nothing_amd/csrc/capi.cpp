@@ -122,6 +122,44 @@ nof_status nof_mipnerf_create(const nof_config* cfg, nof_mipnerf** out) {
     *out = h;
   });
 }
+nof_status nof_mipnerf_create_ex(const nof_config* cfg, const nof_model_ext* ext, nof_mipnerf** out) {
+  return guard([&] {
+    ARG(out);
+    nof_config c;
+    if (cfg) c = *cfg; else nof_config_default(&c);
+    int views = 0, dim = 0;
+    if (ext) {  // (a longer struct of a later header: its first fields are these)
+      if (ext->size < sizeof(nof_model_ext))
+        throw Error(NOF_ERR_INVALID_ARG, "invalid argument: nof_model_ext.size is smaller than the struct");
+      views = ext->appearance_views;
+      dim = ext->appearance_dim;
+    }
+    check_model(c, views, dim);  // every refusal before any device call
+    if (dim == 0) views = 0;     // exactly nof_mipnerf_create
+    KEEP_DEVICE;
+    auto* h = new nof_mipnerf{nullptr};
+    try { h->impl = new AcceleratedMipNeRF(c, views, dim); } catch (...) { delete h; throw; }
+    *out = h;
+  });
+}
+nof_status nof_mipnerf_appearance(nof_mipnerf* h, float** dev_table, float** dev_grad, int32_t* views, int32_t* dim) {
+  return guard([&] {
+    ARG(h && dev_table && dev_grad && views && dim);
+    AcceleratedMLP* m = h->impl->mlp;
+    if (m->appearance_dim() <= 0)
+      throw Error(NOF_ERR_INVALID_ARG, "the model has no appearance embeddings (nof_mipnerf_create_ex)");
+    *dev_table = m->appearance_table();
+    *dev_grad = m->appearance_grad();
+    *views = m->appearance_views();
+    *dim = m->appearance_dim();
+  });
+}
+nof_status nof_mipnerf_set_ray_views(nof_mipnerf* h, const int32_t* dev_view_ids) {
+  return guard([&] { ARG(h); h->impl->set_ray_views(dev_view_ids); });
+}
+nof_status nof_mipnerf_set_render_appearance(nof_mipnerf* h, int32_t view) {
+  return guard([&] { ARG(h); h->impl->set_render_appearance(view); });
+}
 nof_status nof_mipnerf_destroy(nof_mipnerf* h) {
   return guard([&] {
     if (!h) return;
@@ -182,7 +220,8 @@ nof_status nof_device_checks(uint32_t* bits, int32_t clear) {
     NOF_HIP(hipDeviceSynchronize());
     const bool c = clear != 0;
     *bits = nof::check_unit_sampling(c) | nof::check_unit_mlp_fwd16(c) | nof::check_unit_mlp_bwd16(c) |
-            nof::check_unit_wgrad(c) | nof::check_unit_dataset(c) | nof::check_unit_view(c);
+            nof::check_unit_wgrad(c) | nof::check_unit_dataset(c) | nof::check_unit_view(c) |
+            nof::check_unit_appearance(c);
 #else
     (void)clear;
     throw Error(NOF_ERR_UNSUPPORTED, "device checks are compiled only into lib/libnof_check.so (make check)");
@@ -401,6 +440,13 @@ nof_status nof_dataset_pose_grad(nof_dataset* ds, int32_t n, const float* dev_o_
     ARG(ds && dev_o_grad && dev_d_grad && dev_pose_grad);
     KEEP_DEVICE;  // (pose_grad selects the dataset's device once its arguments have passed)
     ds->impl->pose_grad(n, dev_o_grad, dev_d_grad, dev_pose_grad, accumulate, (hipStream_t)stream);
+  });
+}
+nof_status nof_dataset_batch_views(nof_dataset* ds, int32_t n, int32_t* dev_view_ids, void* stream) {
+  return guard([&] {
+    ARG(ds && dev_view_ids);
+    KEEP_DEVICE;  // (batch_views selects the dataset's device once its arguments have passed)
+    ds->impl->batch_views(n, dev_view_ids, (hipStream_t)stream);
   });
 }
 nof_status nof_dataset_get_poses(nof_dataset* ds, float* host_poses) {
@@ -904,6 +950,23 @@ nof_status nof_kernel_adam(int64_t n, float* p, const float* g, float* m, float*
     const float inv1 = 1.0f / (1.0f - std::pow(0.9f, (float)it));
     const float inv2 = 1.0f / (1.0f - std::pow(0.999f, (float)it));
     NOF_HIP(nof::launch_adam(n, p, g, m, v, lr, inv1, inv2, (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_appearance_gather(int32_t n, int32_t vd, int32_t dim, int32_t views, const float* enc_dir,
+                                        const float* table, const int32_t* ids, int32_t const_view, float* out,
+                                        void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && vd >= 0 && dim >= 1 && dim <= 256 && views >= 1 && (vd == 0 || enc_dir) && table && out);
+    NOF_HIP(nof::launch_appearance_gather(n, vd, dim, views, enc_dir, table, ids, const_view, out,
+                                          (hipStream_t)stream));
+  });
+}
+nof_status nof_kernel_appearance_grad(int32_t n, int32_t dim, int32_t views, const int32_t* ids, const float* d_app,
+                                      float* d_table, int32_t accumulate, void* stream) {
+  return guard([&] {
+    ARG(n >= 0 && dim >= 1 && dim <= 256 && views >= 1 && ids && d_app && d_table);
+    ARG(accumulate == 0 || accumulate == 1);
+    NOF_HIP(nof::launch_appearance_grad(n, dim, views, ids, d_app, nullptr, d_table, accumulate, (hipStream_t)stream));
   });
 }
 nof_status nof_kernel_gemm_h(const nof_gemm_args* g, void* stream) {

@@ -133,11 +133,33 @@ static void check_cfg(const nof_config& c) {
                 "path, every network)");
 }
 
+// the network is not the reference's, or the mode / option is one only the any-shape path has
+static bool any_shape(const nof_config& c) {
+  return !(c.net_depth == 8 && c.net_width == 256 && c.net_depth_condition == 1 && c.net_width_condition == 128 &&
+           c.skip_layer == 4 && c.min_deg_point == 0 && c.max_deg_point == 16 && c.deg_view == 4) ||
+         c.precision == NOF_PRECISION_F16_PRODUCTS || c.stop_level_grad == 0;
+}
+
+void check_model(const nof_config& c, int app_views, int app_dim) {
+  check_cfg(c);
+  NOF_REQUIRE(app_dim >= 0 && app_dim <= 256, "appearance_dim must be in [0, 256]");
+  if (app_dim == 0) return;
+  NOF_REQUIRE(app_views > 0, "appearance_dim > 0 needs appearance_views > 0");
+  NOF_REQUIRE((int64_t)app_views * app_dim < ((int64_t)1 << 31), "appearance table too large (views * dim >= 2^31)");
+  if (!any_shape(c))
+    throw Error(NOF_ERR_UNSUPPORTED,
+                "appearance embeddings need the any-shape path: the fused 8x256 kernels have no per-ray operand "
+                "beyond the view encoding (use NOF_PRECISION_F16_PRODUCTS, or NOF_PRECISION_F32 with "
+                "stop_level_grad = 0)");
+}
+
 // ------------------------------------------------------------------------------------------------
 // AcceleratedMLP
 // ------------------------------------------------------------------------------------------------
-AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cfg) : cfg_(cfg) {
-  check_cfg(cfg);
+AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cfg, int app_views, int app_dim)
+    : cfg_(cfg) {
+  check_model(cfg, app_views, app_dim);
+  if (app_dim > 0) { gV_ = app_views; gG_ = app_dim; }
   NOF_REQUIRE(deg_point == cfg.max_deg_point - cfg.min_deg_point && deg_view == cfg.deg_view,
               "AcceleratedMLP(deg_point, deg_view) must match the config");
   NOF_HIP(hipSetDevice(cfg.device));
@@ -148,7 +170,8 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
   aligned_ = cfg.grad_buckets != 0;
 
   // layer dims (get_layer_sizes MLPcpp:131-154, generalised as MLP.cs:64-86): trunk 0..D-1 (the IPE
-  // concatenated into every skip-th layer after the first), density D, view D+1 ([h | view PE]),
+  // concatenated into every skip-th layer after the first), density D, view D+1 ([h | view PE], with appearance
+  // embeddings [h | view PE | E[view]]),
   // condition layers D+2..D+Dc, rgb D+Dc+1
   const int D = cfg.net_depth, W = cfg.net_width, Dc = cfg.net_depth_condition, Wc = cfg.net_width_condition;
   const int pos = 6 * (cfg.max_deg_point - cfg.min_deg_point), dir = 3 * (2 * cfg.deg_view + 1);
@@ -156,7 +179,7 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
   out_.resize(L); in_.resize(L); woff_.resize(L); boff_.resize(L);
   for (int l = 0; l < D; ++l) { out_[l] = W; in_[l] = l == 0 ? pos : (l % cfg.skip_layer == 0 ? W + pos : W); }
   out_[D] = 1; in_[D] = W;
-  out_[D + 1] = Wc; in_[D + 1] = W + dir;
+  out_[D + 1] = Wc; in_[D + 1] = W + dir + gG_;
   for (int i = 1; i < Dc; ++i) { out_[D + 1 + i] = Wc; in_[D + 1 + i] = Wc; }
   out_[D + 1 + Dc] = 3; in_[D + 1 + Dc] = Wc;
   size_t o = 0;
@@ -165,9 +188,7 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
   NOF_REQUIRE(o < (size_t)1 << 31, "network too large");
   P_ = o;
   // (F16_PRODUCTS is the any-shape path's mode: the reference network runs there too)
-  generic_ = !(D == 8 && W == 256 && Dc == 1 && Wc == 128 && cfg.skip_layer == 4 && cfg.min_deg_point == 0 &&
-               cfg.max_deg_point == 16 && cfg.deg_view == 4) ||
-             cfg.precision == NOF_PRECISION_F16_PRODUCTS || cfg.stop_level_grad == 0;
+  generic_ = any_shape(cfg);
   cross_ = cfg.stop_level_grad == 0 && cfg.num_levels > 1;  // (one level: nothing crosses)
 
   params_.alloc(P_);
@@ -305,6 +326,7 @@ void AcceleratedMLP::forward_fused(int level, int n, int samples, const float* t
     NOF_HIP(nof::launch_encode_g(n, samples, G.mean.p, G.cov.p, dirs, gmin_deg_, gP_, gVd_, G.enc_pos.p, G.enc_dir.p,
                                  st_, &v));
     tally(v);
+    if (gG_) appearance_gather(level, n);
     te(kTMlpFwd);
     gen_forward(level, G.enc_pos.p, G.enc_dir.p);
     return;
@@ -332,6 +354,7 @@ std::pair<float*, float*> AcceleratedMLP::get_output(const float* enc_pos, const
     NOF_HIP(hipMemcpyAsync(G.enc_pos.p, enc_pos, (size_t)M * gP_ * sizeof(float), hipMemcpyDeviceToDevice, st_));
     NOF_HIP(hipMemcpyAsync(G.enc_dir.p, enc_dir, (size_t)n_rays * gVd_ * sizeof(float), hipMemcpyDeviceToDevice,
                            st_));
+    if (gG_) appearance_gather(level, n_rays);  // (no per-ray ids on this entry: the constant render view)
     gen_forward(level, G.enc_pos.p, G.enc_dir.p);
     return {lv_[level].sigma.p, lv_[level].rgb.p};
   }
@@ -867,6 +890,7 @@ void AcceleratedMLP::gen_alloc() {
     G.mean.alloc(3 * M); G.cov.alloc(3 * M);
     G.enc_pos.alloc(M * gP_);
     G.enc_dir.alloc((size_t)cfg_.max_rays * gVd_);
+    if (gG_) G.edx.alloc((size_t)cfg_.max_rays * (gVd_ + gG_));
     G.h.alloc((size_t)gD_ * M * gW_);
     G.hc.alloc((size_t)gDc_ * M * gWc_);
     G.z.alloc(4 * M);
@@ -881,6 +905,15 @@ void AcceleratedMLP::gen_alloc() {
   gd1_.alloc((size_t)max_M_ * Wm);
   gdz_.alloc((size_t)max_M_ * 4);
   gray_.alloc((size_t)cfg_.max_rays * gWc_);
+  if (gG_) {  // the table starts at zero: a new model renders as one without the option would
+    const size_t T = (size_t)gV_ * gG_;
+    app_table_.alloc(T);
+    app_grad_.alloc(T);
+    app_step_.alloc(T);
+    NOF_HIP(hipMemset(app_table_.p, 0, T * sizeof(float)));
+    NOF_HIP(hipMemset(app_grad_.p, 0, T * sizeof(float)));
+    gdapp_.alloc((size_t)cfg_.max_rays * gG_);
+  }
   if (cross_) denc_alloc(1);  // levels >= 1 only
   if (f16_products()) {
     amax_.alloc(NL);
@@ -943,6 +976,18 @@ void AcceleratedMLP::set_contraction(int mode) {
   contraction_ = mode;
 }
 
+void AcceleratedMLP::set_render_appearance(int view) {
+  NOF_REQUIRE(gG_ > 0, "the model has no appearance embeddings (nof_mipnerf_create_ex)");
+  NOF_REQUIRE(view >= -1 && view < gV_, "render appearance view out of range");
+  app_const_ = view;
+}
+
+void AcceleratedMLP::appearance_gather(int level, int n) {
+  GenLevel& G = gl_[level];
+  NOF_HIP(nof::launch_appearance_gather(n, gVd_, gG_, gV_, G.enc_dir.p, app_table_.p, app_ids_, app_const_, G.edx.p,
+                                        st_));
+}
+
 void AcceleratedMLP::gen_wgrad(float* dst, int64_t ld, const float* dz, int64_t ldz, int nout, nof::GemmSrc x,
                                int ncols, int M, int accumulate, float* bias_dst, const uint32_t* scale) {
   int ks, kc;
@@ -975,6 +1020,8 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
   GenLevel& G = gl_[level];
   const int M = L.M, S = L.S, D = gD_, W = gW_, Dc = gDc_, Wc = gWc_, P = gP_, Vd = gVd_, lr = D + 1 + Dc;
   G.ep = ep; G.ed = ed;
+  const float* vx = gG_ ? G.edx.p : ed;  // the view layer's per-ray operand [n][Vx]
+  const int Vx = Vd + gG_;
   const float* prm = params_.p;
   auto H = [&](int l) { return G.h.p + (size_t)l * M * W; };
   auto Hc = [&](int i) { return G.hc.p + (size_t)i * M * Wc; };
@@ -1011,7 +1058,7 @@ void AcceleratedMLP::gen_forward(int level, const float* ep, const float* ed) {
     a.M = M; a.N = Wc;
     if (i == 0) {
       a.K1 = W; a.A1 = gsrc(H(D - 1), W, 1);
-      a.K2 = Vd; a.A2 = gsrc(ed, Vd, 1, S);
+      a.K2 = Vx; a.A2 = gsrc(vx, Vx, 1, S);
     } else {
       a.K1 = Wc; a.A1 = gsrc(Hc(i - 1), Wc, 1);
     }
@@ -1055,6 +1102,9 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
   NOF_REQUIRE(!rays || (rg_job_.n == L.n && rg_job_.t[level]), "the ray-gradient job is not this step's");
   want_denc = want_denc || rays;
   const int M = L.M, S = L.S, D = gD_, W = gW_, Dc = gDc_, Wc = gWc_, P = gP_, Vd = gVd_, lr = D + 1 + Dc;
+  const float* vx = gG_ ? G.edx.p : G.ed;  // the view layer's per-ray operand [n][Vx]
+  const int Vx = Vd + gG_;
+  const bool app = !dry && gG_ > 0 && app_job_.ids != nullptr;  // the owner's step: dE too
   const float* prm = params_.p;
   float* gr = grads_.p;
   auto H = [&](int l) { return G.h.p + (size_t)l * M * W; };
@@ -1106,8 +1156,8 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     dx(cur, Wc, Wc, l, D + i - 1, Hc(i - 1), Wc, nxt);
     std::swap(cur, nxt);
   }
-  // view layer: columns [0, W) against h_{D-1}, [W, W + Vd) against the ray's view PE
-  gen_wgrad(gr + woff_[D + 1], W + Vd, cur, Wc, Wc, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D + 1], sc);
+  // view layer: columns [0, W) against h_{D-1}, [W, W + Vx) against the ray's view PE (and embedding row)
+  gen_wgrad(gr + woff_[D + 1], W + Vx, cur, Wc, Wc, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D + 1], sc);
   // (the view PE is per ray: dW_pe = sum over rays of (sum over the ray's samples of dZ) PE(ray)).  In every
   // mode on fp32 k_gemm: a sum over up to 512 samples does not share the head deltas' range (the scale
   // leaves 2^7 above their maximum), and with k = rays the product's FLOPs are negligible
@@ -1118,12 +1168,20 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
       nof::GemmArgs a;
       a.M = M / S; a.N = Vd; a.K1 = Wc;
       a.A1 = gsrc(gray_.p, Wc, 1);
-      a.B1 = gsrc(prm + woff_[D + 1] + W, 1, W + Vd);
+      a.B1 = gsrc(prm + woff_[D + 1] + W, 1, W + Vx);
       a.C = gddir_.p; a.ci = Vd; a.cj = 1;
       gen_product(a, 1, false, true);
     }
+    if (app) {  // dApp[r][g] = sum_o gray[r][o] W_view[o][W + Vd + g], as dDir
+      nof::GemmArgs a;
+      a.M = M / S; a.N = gG_; a.K1 = Wc;
+      a.A1 = gsrc(gray_.p, Wc, 1);
+      a.B1 = gsrc(prm + woff_[D + 1] + W + Vd, 1, W + Vx);
+      a.C = gdapp_.p; a.ci = gG_; a.cj = 1;
+      gen_product(a, 1, false, true);
+    }
   }
-  gen_wgrad(gr + woff_[D + 1] + W, W + Vd, gray_.p, Wc, Wc, gsrc(G.ed, 1, Vd), Vd, M / S, acc);
+  gen_wgrad(gr + woff_[D + 1] + W, W + Vx, gray_.p, Wc, Wc, gsrc(vx, 1, Vx), Vx, M / S, acc);
   // density head
   gen_wgrad(gr + woff_[D], W, dz + 3, 4, 1, gsrc(H(D - 1), 1, W), W, M, acc, gr + boff_[D], sc);
   if (!dry) {  // dh_{D-1} = dZ_view W_view[:, :W] + dz_density w_D (MLPcs:148-153, D11), masked
@@ -1131,7 +1189,7 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     a.M = M; a.N = W; a.K1 = Wc; a.K2 = 1;
     a.A1 = gsrc(cur, Wc, 1);
     a.A2 = gsrc(dz + 3, 4, 1);
-    a.B1 = gsrc(prm + woff_[D + 1], 1, W + Vd);
+    a.B1 = gsrc(prm + woff_[D + 1], 1, W + Vx);
     a.B2 = gsrc(prm + woff_[D], 1, 0);
     a.C = nxt; a.ci = W; a.cj = 1;
     if (sc) { a.scale_amax = sc; a.scale_src = 1; }  // (A2 = dz_density is a delta as well)
@@ -1217,6 +1275,17 @@ void AcceleratedMLP::gen_backward(int level, const float* color_grad, const floa
     NOF_HIP(nof::launch_ray_grad(ra, st_));
     rg_job_.first = false;
   }
+  if (app) {  // before the next level's backward overwrites dApp.  The step's levels sum in launch order: all but
+              // the last into app_step_ (the first overwrites), the last adds that sum and meets dE with the job's flag
+    const bool last = --app_job_.left <= 0;
+    if (last)
+      NOF_HIP(nof::launch_appearance_grad(L.n, gG_, gV_, app_job_.ids, gdapp_.p, app_job_.first ? nullptr : app_step_.p,
+                                          app_grad_.p, app_job_.accumulate, st_));
+    else
+      NOF_HIP(nof::launch_appearance_grad(L.n, gG_, gV_, app_job_.ids, gdapp_.p, nullptr, app_step_.p,
+                                          app_job_.first ? 0 : 1, st_));
+    app_job_.first = false;
+  }
   wg_jobs_.clear();
 }
 
@@ -1234,12 +1303,12 @@ float* const* AcceleratedMLP::gen_publish(bool buckets) {
 // ------------------------------------------------------------------------------------------------
 // AcceleratedMipNeRF
 // ------------------------------------------------------------------------------------------------
-AcceleratedMipNeRF::AcceleratedMipNeRF(const nof_config& cfg) : mlp(nullptr), cfg_(cfg) {
-  check_cfg(cfg);
+AcceleratedMipNeRF::AcceleratedMipNeRF(const nof_config& cfg, int app_views, int app_dim) : mlp(nullptr), cfg_(cfg) {
+  check_model(cfg, app_views, app_dim);
   NOF_HIP(hipSetDevice(cfg.device));
   st_ = (hipStream_t)cfg.stream;
   seed_ = cfg.seed;
-  mlp = new AcceleratedMLP(cfg.max_deg_point - cfg.min_deg_point, cfg.deg_view, cfg);
+  mlp = new AcceleratedMLP(cfg.max_deg_point - cfg.min_deg_point, cfg.deg_view, cfg, app_views, app_dim);
   mlp->timer = &timer;
   const size_t N = cfg.max_rays;
   o_.alloc(3 * N); d_.alloc(3 * N); radii_.alloc(N); nears_.alloc(N); fars_.alloc(N); lm_.alloc(N); pix_.alloc(3 * N);
@@ -1272,11 +1341,23 @@ AcceleratedMipNeRF::~AcceleratedMipNeRF() {
   delete mlp;
 }
 
+void AcceleratedMipNeRF::set_ray_views(const int32_t* ids) {
+  NOF_REQUIRE(has_appearance(), "the model has no appearance embeddings (nof_mipnerf_create_ex)");
+  mlp->set_ray_views(ids);
+}
+
+void AcceleratedMipNeRF::require_ray_views() const {
+  NOF_REQUIRE(!has_appearance() || mlp->ray_views(),
+              "a gradient step of an appearance model needs its ray views (nof_mipnerf_set_ray_views before every "
+              "step)");
+}
+
 float* const* AcceleratedMipNeRF::GetGradient(int n, const float* origins, const float* directions,
                                               const float* radii, const float* nears, const float* fars,
                                               const float* loss_mults, nof_output_grad_fn cb, void* user) {
   NOF_REQUIRE(n > 0 && n <= cfg_.max_rays, "ray count out of range");
   NOF_REQUIRE(origins && directions && radii && nears && fars && loss_mults && cb, "null argument");
+  require_ray_views();
   // loss-mult sum as float (D14: the reference truncates it into an int, MNcpp:61-65)
   float msum = 0.0f;
   for (int i = 0; i < n; ++i) msum += loss_mults[i];
@@ -1296,6 +1377,7 @@ float* const* AcceleratedMipNeRF::GetGradientDevice(int n, const float* o, const
   NOF_REQUIRE(o && d && radii && nears && fars && loss_mults && pixels, "null argument");
   NOF_REQUIRE(msum > 0.0f, "loss_mult_sum must be > 0");
   NOF_REQUIRE((flags & ~(uint32_t)(NOF_GRAD_ACCUMULATE | NOF_GRAD_PUBLISH)) == 0, "unknown gradient flags");
+  require_ray_views();
   return run(n, o, d, radii, nears, fars, loss_mults, pixels, msum, nullptr, nullptr, flags);
 }
 
@@ -1307,6 +1389,12 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
   static const char* const kBwd[] = {"nof:backward"};
   const int L = cfg_.num_levels;
   TraceRange step_range("nof:get_gradient");
+  // appearance embeddings: the step's view ids feed every level's gather and its dE sum; they hold for this call
+  struct ViewScope {
+    AcceleratedMLP* m;
+    ~ViewScope() { m->set_ray_views(nullptr); m->set_appearance_job(nullptr, 0, 0); }
+  } view_scope{mlp};
+  if (has_appearance()) mlp->set_appearance_job(mlp->ray_views(), (flags & NOF_GRAD_ACCUMULATE) ? 1 : 0, L);
   nof::StratArgs sa;  // level 0's t-values, by the pack launch's extra blocks
   sa.n = n; sa.S = cfg_.num_samples[0]; sa.nears = nears; sa.fars = fars; sa.randomized = cfg_.randomized;
   sa.lindisp = cfg_.lindisp; sa.seed = seed_; sa.step = step_; sa.ray_base = ray_base_; sa.t = t_[0].p;
@@ -1595,6 +1683,10 @@ void AcceleratedMipNeRF::Render(int n, const float* o, const float* d, const flo
   NOF_REQUIRE(n > 0 && n <= cfg_.max_rays, "ray count out of range");
   NOF_REQUIRE(o && d && radii && nears && fars && out, "null argument");
   const int L = cfg_.num_levels;
+  struct ViewScope {  // (appearance embeddings: per-ray ids hold for this call)
+    AcceleratedMLP* m;
+    ~ViewScope() { m->set_ray_views(nullptr); }
+  } view_scope{mlp};
   mlp->pack_weights();
   for (int lv = 0; lv < L; ++lv) {  // MNcs:40-95
     const int S = cfg_.num_samples[lv];

@@ -104,7 +104,9 @@ class AcceleratedMLP {
   // NOF_PRECISION_F16_PRODUCTS: the any-shape path (generic.hip, gemm_h.hip) runs it
   bool generic() const { return generic_; }
 
-  AcceleratedMLP(int deg_point, int deg_view, const nof_config& cfg);  // MLPcpp:168-213
+  // app_views, app_dim: per-view appearance embeddings (include/nof.h nof_mipnerf_create_ex; 0, 0 = none)
+  AcceleratedMLP(int deg_point, int deg_view, const nof_config& cfg, int app_views = 0,
+                 int app_dim = 0);  // MLPcpp:168-213
   ~AcceleratedMLP() = default;
 
   std::vector<int> get_layer_sizes() const;  // MLPcpp:131-154
@@ -195,8 +197,31 @@ class AcceleratedMLP {
   // adjoint.  A hyper-parameter: nothing is allocated, it holds from the next call on.
   void set_contraction(int mode);
   int contraction() const { return contraction_; }
+  // Per-view appearance embeddings (include/nof.h nof_mipnerf_create_ex; any-shape path only): the
+  // table E [V][G] and its gradient live outside the arena.  Every forward gathers the view layer's per-ray operand
+  // [view PE | E[id]] (k_appearance_gather) by the ids of set_ray_views, or by the constant render view without
+  // them.  While the owner has a job set (a gradient step: its rays' ids), every level's backward also forms
+  // dApp = (the view layer's per-ray deltas) W_view[:, W + Vd :] and sums it per view (k_appearance_grad): the job's
+  // `levels` backward calls sum in call order, all but the last into a buffer of the step's own; the last adds that
+  // and overwrites dE or, accumulate, adds to it once (two accumulated steps of one batch: exactly twice its dE).
+  int appearance_views() const { return gV_; }
+  int appearance_dim() const { return gG_; }
+  float* appearance_table() const { return app_table_.p; }
+  float* appearance_grad() const { return app_grad_.p; }
+  void set_ray_views(const int32_t* ids) { app_ids_ = ids; }
+  const int32_t* ray_views() const { return app_ids_; }
+  void set_render_appearance(int view);
+  void set_appearance_job(const int32_t* ids, int accumulate, int levels) {
+    app_job_ = AppJob{ids, accumulate, levels, true};
+  }
 
  private:
+  struct AppJob {
+    const int32_t* ids = nullptr;
+    int accumulate = 0;
+    int left = 0;  // backward calls still to come
+    bool first = true;
+  };
   struct Schedule {
     DevBuf<nof::WgProblem> probs;
     DevBuf<nof::WgItem> items;
@@ -252,6 +277,7 @@ class AcceleratedMLP {
   int gD_ = 0, gW_ = 0, gDc_ = 0, gWc_ = 0, gskip_ = 0, gmin_deg_ = 0, gP_ = 0, gVd_ = 0;
   struct GenLevel {
     DevBuf<float> mean, cov, enc_pos, enc_dir;  // the fused path's encodings ([M][P], [n][Vd])
+    DevBuf<float> edx;                          // appearance models: the per-ray operand [n][Vd + G]
     DevBuf<float> h, hc, z;                     // trunk [D][M][W], condition [Dc][M][Wc], heads [M][4]
     const float *ep = nullptr, *ed = nullptr;   // the encodings the last forward read (API path: the caller's)
     // ReLU mask bits of the trunk layers then the condition layers [D + Dc][M][4] (gemm_ws.hip), and which
@@ -282,6 +308,14 @@ class AcceleratedMLP {
   int contraction_ = NOF_CONTRACT_NONE;
   RayGradJob rg_job_;
   DevBuf<float> gddir_, rg_o_, rg_d_;  // dL/d(view PE) [rays][Vd]; dL/do, dL/dd [rays][3]
+  int gV_ = 0, gG_ = 0;                  // appearance embeddings: views, dim (0: none)
+  DevBuf<float> app_table_, app_grad_;   // E, dE [V][G]
+  DevBuf<float> app_step_;               // a step's sum over its levels but the last [V][G]
+  DevBuf<float> gdapp_;                  // dL/d(the rays' embedding rows) [rays][G], one level's
+  const int32_t* app_ids_ = nullptr;     // the next ray-casting call's view ids (the owner resets it)
+  int app_const_ = -1;                   // the view of calls without ids (-1: zeros)
+  AppJob app_job_;
+  void appearance_gather(int level, int n);  // G.edx of the level from its enc_dir and the ids / constant view
   // non-null: gen_backward launches nothing and gen_wgrad records its split-K slab need here instead (the
   // slab is sized at construction by a dry run of the same call sequence a step makes)
   size_t* wg_need_ = nullptr;
@@ -316,12 +350,15 @@ void dp_model_destroyed(nof_dp* dp, class AcceleratedMipNeRF* model);
 // num_layers layers; returns the span count (host only, no device needed).
 int grad_bucket_spans(const int* sizes, int num_layers, int b, int64_t* off, int64_t* cnt);
 
+// nof_mipnerf_create_ex's refusals (config and extension), before any device call
+void check_model(const nof_config& cfg, int app_views, int app_dim);
+
 // ---------------------------------------------------------------------------------------------
 // AcceleratedMipNeRF (AcceleratedMipNeRF.h:10-41; MNcpp:7-176)
 // ---------------------------------------------------------------------------------------------
 class AcceleratedMipNeRF {
  public:
-  explicit AcceleratedMipNeRF(const nof_config& cfg);
+  explicit AcceleratedMipNeRF(const nof_config& cfg, int app_views = 0, int app_dim = 0);
   ~AcceleratedMipNeRF();
   AcceleratedMLP* mlp;  // public field, as AcceleratedMipNeRF.h:18
 
@@ -354,6 +391,12 @@ class AcceleratedMipNeRF {
   // makes from the next call on (training step, Render, the dataset's render_view) and of their adjoints
   void set_contraction(int mode) { mlp->set_contraction(mode); }
   int contraction() const { return mlp->contraction(); }
+  // Appearance embeddings (include/nof.h nof_mipnerf_set_ray_views / _set_render_appearance): the ids hold for the
+  // next gradient step or Render, which resets them
+  bool has_appearance() const { return mlp->appearance_dim() > 0; }
+  void set_ray_views(const int32_t* ids);
+  void set_render_appearance(int view) { mlp->set_render_appearance(view); }
+  void require_ray_views() const;  // a gradient step of an appearance model without ids: NOF_ERR_INVALID_ARG
   uint32_t numeric_status(bool clear);  // NOF_NUMERIC_* bits since the last clear (synchronises)
   // Forward-only two-level render (MipNerfModel.Call, MNcs:36-97, with its D22 defects fixed):
   // per level comp_rgb [n][3], distance [n], acc [n] (device, borrowed until the next call).

@@ -516,6 +516,11 @@ void dp_train_step(int n, nof_dp* const* dps, AcceleratedMipNeRF* const* models,
                    float* msum_out) {
   NOF_REQUIRE(n >= 1 && n <= 64 && models && adams && datasets, "bad train-step arguments");
   for (int r = 0; r < n; ++r) NOF_REQUIRE(models[r] && adams[r] && datasets[r], "null replica");
+  for (int r = 0; r < n; ++r)
+    if (models[r]->has_appearance())
+      throw Error(NOF_ERR_UNSUPPORTED,
+                  "nof_dp_train_step does not step a model with appearance embeddings: the table's all-reduce and its "
+                  "Adam are the caller's (nof_mipnerf_appearance, nof_dp_allreduce)");
   // the replicas' shard indices: n replicas in this process, or this process's rank of `world`
   int world = n, rank0 = 0;
   bool attached = false;

@@ -295,6 +295,17 @@ void RayDataset::pose_grad(int n, const float* dev_o_grad, const float* dev_d_gr
   NOF_HIP(nof::launch_pose_grad(layout_, n, idx_.p, dev_o_grad, dev_d_grad, dev_pose_grad, accumulate, st));
 }
 
+void RayDataset::batch_views(int n, int32_t* dev_view_ids, hipStream_t st) {
+  if (!image_backed())
+    throw Error(NOF_ERR_UNSUPPORTED, "batch_views needs an image-backed dataset (nof_dataset_from_images): record "
+                                     "files carry no view");
+  NOF_REQUIRE(dev_view_ids != nullptr, "null argument");
+  NOF_REQUIRE(last_n_ > 0, "batch_views before nof_dataset_next");
+  NOF_REQUIRE(n > 0 && n <= last_n_, "n exceeds the last batch");
+  NOF_HIP(hipSetDevice(device_));
+  NOF_HIP(nof::launch_batch_views(layout_, n, idx_.p, dev_view_ids, st));
+}
+
 void RayDataset::get_poses(float* host_poses) {
   if (!image_backed())
     throw Error(NOF_ERR_UNSUPPORTED, "get_poses needs an image-backed dataset (nof_dataset_from_images)");

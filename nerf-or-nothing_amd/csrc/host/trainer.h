@@ -66,6 +66,9 @@ class RayDataset {
   // batch's rays summed per view into dev_pose_grad [V][12] (dataset.hip k_pose_grad), on st.
   void pose_grad(int n, const float* dev_o_grad, const float* dev_d_grad, float* dev_pose_grad, int accumulate,
                  hipStream_t st);
+  // Image-backed (else NOF_ERR_UNSUPPORTED): the view of every ray of the LAST next() batch -> dev_view_ids [n]
+  // (dataset.hip k_batch_views), on st.
+  void batch_views(int n, int32_t* dev_view_ids, hipStream_t st);
   // The pose table (V x 12, host).  set_poses waits for the device's work, then copies: the next gather and
   // render_view read the new poses.
   void get_poses(float* host_poses);

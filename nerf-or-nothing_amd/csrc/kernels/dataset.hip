@@ -181,6 +181,23 @@ hipError_t launch_pose_grad(const MultiscaleLayout& L, int n, const int* idx, co
   return hipGetLastError();
 }
 
+// The view of each ray of a batch (the appearance embeddings' row ids): record_pos of its record index.
+__global__ __launch_bounds__(256) void k_batch_views(MultiscaleLayout L, int n, const int* __restrict__ idx,
+                                                     int* __restrict__ views) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const RecordPos p = record_pos(L, (uint32_t)idx[r]);
+  NOF_DCHECK(p.v >= 0 && p.v < L.num_views, kChkGather);
+  views[r] = p.v;
+}
+
+hipError_t launch_batch_views(const MultiscaleLayout& L, int n, const int* idx, int* views, hipStream_t st) {
+  if (L.num_views <= 0 || n < 0 || !idx || !views) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_batch_views, dim3((n + 255) / 256), dim3(256), 0, st, L, n, idx, views);
+  return hipGetLastError();
+}
+
 // fails kChkSelfTest on purpose: proves a checked build's plumbing (nof_device_checks_selftest)
 __global__ void k_check_selftest(int zero) { NOF_DCHECK(zero != 0, kChkSelfTest); }
 hipError_t launch_check_selftest(hipStream_t st) {

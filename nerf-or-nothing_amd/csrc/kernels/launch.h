@@ -15,6 +15,7 @@ uint32_t check_unit_mlp_bwd16(bool clear);
 uint32_t check_unit_wgrad(bool clear);
 uint32_t check_unit_dataset(bool clear);
 uint32_t check_unit_view(bool clear);
+uint32_t check_unit_appearance(bool clear);
 hipError_t launch_check_selftest(hipStream_t st);  // fails kChkSelfTest on purpose
 
 // ---- sampling.hip (get_sample_t_vals AF:222-242, get_resampled_t_vals AF:246-291) ----------
@@ -411,6 +412,19 @@ hipError_t launch_gather_rays(const float* poses, const float* pyr, const Multis
 // batch's record indices.  A view without a ray: 0, or unchanged when accumulating.
 hipError_t launch_pose_grad(const MultiscaleLayout& L, int n, const int* idx, const float* o_grad, const float* d_grad,
                             float* pose_grad, int accumulate, hipStream_t st);
+// dataset.hip: the view of every record index of a batch of an image-backed scene (record_pos), views [n]
+hipError_t launch_batch_views(const MultiscaleLayout& L, int n, const int* idx, int* views, hipStream_t st);
+
+// ---- appearance.hip: per-view appearance embeddings (include/nof.h nof_mipnerf_create_ex) ----
+// out [n][vd + dim] = [enc_dir row | table[id] row]; id = ids[r], or const_view for every ray when ids == null; an
+// id outside [0, views) reads zeros (with per-ray ids a checked build also sets NOF_CHECK_GATHER)
+hipError_t launch_appearance_gather(int n, int vd, int dim, int views, const float* enc_dir, const float* table,
+                                    const int* ids, int const_view, float* out, hipStream_t st);
+// d_table [views][dim] (+)= the rows of d_app [n][dim] summed per view id in a fixed order (an id outside
+// [0, views) joins no row), plus partial [views][dim] when given (distinct from d_table).  A view without a ray:
+// 0 (+ partial), or unchanged when accumulating.
+hipError_t launch_appearance_grad(int n, int dim, int views, const int* ids, const float* d_app, const float* partial,
+                                  float* d_table, int accumulate, hipStream_t st);
 
 // ---- view.hip: a whole view of an image-backed scene, chunk by chunk (include/nof.h nof_dataset_render_view) ----
 // The rays of pixels [p0, p0 + n) of a w x h view (one scale's row of the MultiscaleLayout), row-major, into a

@@ -65,6 +65,10 @@ _DIST_MULT_OFFSET = nof_config.stop_level_grad.offset + C.sizeof(C.c_int32)
 assert _DIST_MULT_OFFSET + C.sizeof(C.c_float) <= C.sizeof(nof_config), "nof_config: no room for distortion_loss_mult"
 
 
+class nof_model_ext(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("appearance_views", C.c_int32), ("appearance_dim", C.c_int32)]
+
+
 class nof_level_view(C.Structure):
     _fields_ = [("n", C.c_int32), ("samples", C.c_int32)] + [
         (k, C.c_void_p) for k in ("t", "weights", "comp_rgb", "density", "rgb", "density_grad", "rgb_grad")]
@@ -134,6 +138,10 @@ SIGNATURES = {
     "nof_version": [],
     "nof_config_size": [],
     "nof_mipnerf_create": [C.POINTER(nof_config), C.POINTER(P)],
+    "nof_mipnerf_create_ex": [C.POINTER(nof_config), C.POINTER(nof_model_ext), C.POINTER(P)],
+    "nof_mipnerf_appearance": [P, C.POINTER(P), C.POINTER(P), C.POINTER(I32), C.POINTER(I32)],
+    "nof_mipnerf_set_ray_views": [P, P],
+    "nof_mipnerf_set_render_appearance": [P, I32],
     "nof_mipnerf_destroy": [P],
     "nof_mipnerf_get_gradient": [P, I32, P, P, P, P, P, P, OUTPUT_GRAD_FN, P, C.POINTER(PP)],
     "nof_mipnerf_get_gradient_device": [P, I32, P, P, P, P, P, P, P, F, C.POINTER(PP)],
@@ -176,6 +184,7 @@ SIGNATURES = {
     "nof_dataset_scene_info": [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)],
     "nof_dataset_render_view": [P, P, I32, P, I32, U32, C.POINTER(nof_view_out), C.POINTER(nof_view_metrics)],
     "nof_dataset_pose_grad": [P, I32, P, P, P, I32, P],
+    "nof_dataset_batch_views": [P, I32, P, P],
     "nof_dataset_get_poses": [P, P],
     "nof_dataset_set_poses": [P, P],
     "nof_recenter_poses": [P, I32],
@@ -253,6 +262,8 @@ SIGNATURES = {
     "nof_kernel_ray_grad_ex": [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P, I32],
     "nof_kernel_adam": [C.c_int64, P, P, P, P, F, I32, P],
     "nof_kernel_gemm_h": [C.POINTER(nof_gemm_args), P],
+    "nof_kernel_appearance_gather": [I32, I32, I32, I32, P, P, P, I32, P, P],
+    "nof_kernel_appearance_grad": [I32, I32, I32, P, P, P, I32, P],
 }
 _RESTYPE = {"nof_config_default": None, "nof_last_error": C.c_char_p, "nof_version": C.c_char_p,
             "nof_config_size": C.c_size_t,

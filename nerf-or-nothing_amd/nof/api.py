@@ -237,12 +237,20 @@ class AcceleratedMLP:
 class AcceleratedMipNeRF:
     """AcceleratedMipNeRF.h:10-41 (ctor MNcpp:7-50, GetGradient MNcpp:52-144)."""
 
-    def __init__(self, config: L.nof_config | None = None, **overrides):
+    def __init__(self, config: L.nof_config | None = None, appearance_views: int = 0, appearance_dim: int = 0,
+                 **overrides):
+        """appearance_views = V, appearance_dim = G > 0: per-view appearance embeddings (include/nof.h
+        nof_mipnerf_create_ex): a zero-initialised table [V, G] outside the parameter arena, one row per training
+        image, feeds the view layer; any-shape path only (a fused 8x256 model raises NofError(NOF_ERR_UNSUPPORTED))."""
         self.config = config if config is not None else L.default_config(**overrides)
         self._hook_errors = []
         self._bucket_cb = None
         h = C.c_void_p()
-        call("nof_mipnerf_create", C.byref(self.config), C.byref(h))
+        if appearance_views or appearance_dim:
+            ext = L.nof_model_ext(C.sizeof(L.nof_model_ext), int(appearance_views), int(appearance_dim))
+            call("nof_mipnerf_create_ex", C.byref(self.config), C.byref(ext), C.byref(h))
+        else:
+            call("nof_mipnerf_create", C.byref(self.config), C.byref(h))
         self._h = h
         m = C.c_void_p()
         call("nof_mipnerf_mlp", self._h, C.byref(m))
@@ -403,6 +411,24 @@ class AcceleratedMipNeRF:
         out = C.c_int32()
         call("nof_mipnerf_get_contraction", self._h, C.byref(out))
         return out.value
+
+    def appearance(self):
+        """(table_ptr, grad_ptr, V, G): borrowed device pointers to the appearance table E and its gradient dE, each
+        [V, G] (to_numpy / device_tensor).  The caller owns the update: an AcceleratedAdamOptimizer([V * G]) steps
+        ([table_ptr], [grad_ptr]).  A model without appearance raises NofError(NOF_ERR_INVALID_ARG)."""
+        t, g, V, G = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        call("nof_mipnerf_appearance", self._h, C.byref(t), C.byref(g), C.byref(V), C.byref(G))
+        return t.value, g.value, V.value, G.value
+
+    def set_ray_views(self, view_ids) -> None:
+        """The view ids ([n] int32, a device pointer or tensor the caller keeps alive) of the rays of the next
+        gradient step or render_device; that call resets them (None clears them now)."""
+        call("nof_mipnerf_set_ray_views", self._h, _ptr(view_ids) or None)
+
+    def set_render_appearance(self, view: int = -1) -> None:
+        """The view whose embedding calls without per-ray ids use (render_device without ids,
+        RayDataset.render_view, AcceleratedMLP.get_output); -1 (the default): the zero vector."""
+        call("nof_mipnerf_set_render_appearance", self._h, int(view))
 
     def numeric_status(self, clear: bool = True) -> int:
         """NOF_NUMERIC_* bits (non-finite forward outputs / output gradients) since the last clear."""
@@ -699,6 +725,17 @@ class RayDataset:
                               device=torch.device("cuda", self._device))
         call("nof_dataset_pose_grad", self._h, int(n), _ptr(o_grad), _ptr(d_grad), out.data_ptr(), int(accumulate),
              stream)
+        return out
+
+    def batch_views(self, n: int, out=None, stream=None):
+        """The view of every ray of the LAST next() batch -> torch device tensor [n] int32 (include/nof.h
+        nof_dataset_batch_views), enqueued on `stream`: the ids AcceleratedMipNeRF.set_ray_views takes.  A record
+        dataset raises NofError(NOF_ERR_UNSUPPORTED)."""
+        import torch
+
+        if out is None:
+            out = torch.empty((int(n),), dtype=torch.int32, device=torch.device("cuda", self._device))
+        call("nof_dataset_batch_views", self._h, int(n), out.data_ptr(), stream)
         return out
 
     def poses(self) -> np.ndarray:

@@ -11,6 +11,8 @@ never implements.
                                                                 (the scene's poses refined jointly with the field)
     python -m nof.train --scene scene.npz --contract --lindisp --precision f16p
                                                                 (an unbounded scene: space contracted into a ball)
+    python -m nof.train --scene scene.npz --appearance-dim 32 --precision f16p
+                                                                (a learned appearance vector per training image)
 
 One step = dataset batch (device gather) -> AcceleratedMipNeRF.get_gradient_device (fused loss
 gradient) -> [all-reduce of the gradient arena when torch.distributed is initialised] ->
@@ -35,7 +37,7 @@ class Trainer:
                  sync_check_every: int = 0, lr_init=5e-4, lr_final=5e-6, max_steps=1000000, lr_delay_steps=2500, lr_delay_mult=0.01,
                  grad_max_norm: float = 0.0, grad_max_val: float = 0.0, weight_decay_mult: float = 0.0,
                  stats: bool = False, refine_poses: float = 0.0, interlevel_loss_mult: float = 0.0,
-                 contract: bool = False, **config):
+                 contract: bool = False, appearance_dim: int = 0, appearance_lr: float = 1e-3, **config):
         import torch.distributed as dist
 
         self.dist = dist if dist.is_available() and dist.is_initialized() else None
@@ -50,7 +52,20 @@ class Trainer:
         self.lr = dict(lr_init=lr_init, lr_final=lr_final, max_steps=max_steps, lr_delay_steps=lr_delay_steps,
                        lr_delay_mult=lr_delay_mult)
         self.cfg = default_config(device=device, max_rays=batch_size, seed=seed, stream=stream, **config)
-        self.model = api.AcceleratedMipNeRF(self.cfg)
+        # per-view appearance embeddings: one table row per view of the training dataset.  Refused
+        # here, before training, with the library's message: by a dataset without views (a batch's views are asked
+        # for once) and, at the model's creation, by a fused 8x256 precision
+        self.appearance_dim, self.appearance_lr = int(appearance_dim), float(appearance_lr)
+        app_views = 0
+        if self.appearance_dim:
+            dataset.next(batch_size, seed, 0, 0, stream, with_sum=False)
+            self.view_ids = dataset.batch_views(batch_size, stream=stream)
+            app_views = dataset.scene_info()["num_views"]
+        self.model = api.AcceleratedMipNeRF(self.cfg, appearance_views=app_views, appearance_dim=self.appearance_dim)
+        self.app_adam = None
+        if self.appearance_dim:  # the table is the caller's to step: a second optimizer over its V * G floats
+            self.app_table, self.app_grad, V, G = self.model.appearance()
+            self.app_adam = api.AcceleratedAdamOptimizer([V * G], self.cfg)
         # Config.GradMaxNorm / GradMaxVal / WeightDecayMult (TrainState.cs:58-59,70): hyper-parameters, not
         # checkpoint state, so a resumed run passes them again
         self.adam = api.AcceleratedAdamOptimizer(self.model.GetLayerSizes(), self.cfg, grad_max_norm=grad_max_norm,
@@ -107,9 +122,19 @@ class Trainer:
             msum = float(t.item())
         self.model.set_rng(self.seed, step, ray_base)
         p = {k: v[0] for k, v in b.items()}
+        if self.app_adam is not None:  # this batch's view ids, for this step alone
+            self.ds.batch_views(self.n, out=self.view_ids, stream=self.stream)
+            self.model.set_ray_views(self.view_ids)
         grads = self.model.get_gradient_device(self.n, p["o"], p["d"], p["radius"], p["near"], p["far"],
                                                p["lossmult"], p["pix"], msum)
         self.adam.step(self.params, grads, api.learning_rate_decay(step, **self.lr))
+        if self.app_adam is not None:
+            if self.dist is not None:  # every rank's shard of the batch (the table is outside the gradient arena)
+                V, G = self.model.appearance()[2:]
+                api.call("nof_stream_sync", self.stream)
+                self.dist.all_reduce(api.device_tensor(self.app_grad, (V, G),
+                                                       device=torch.device("cuda", self.device)))
+            self.app_adam.step([self.app_table], [self.app_grad], self.appearance_lr)
         if self.refiner is not None:  # this batch's pose gradient; the corrected poses make the next batch's rays
             self.refiner.step(self.model, self.n, self.dist)
         self.step_idx = step
@@ -142,6 +167,22 @@ class Trainer:
             os.makedirs(self.ckpt_dir, exist_ok=True)
             self.save(os.path.join(self.ckpt_dir, f"ckpt_{step:08d}.nof"))
             self.save_poses()
+            self.save_appearance()
+
+    def appearance(self) -> np.ndarray:
+        """--appearance-dim: the appearance table [V, G] (host copy)"""
+        api.call("nof_stream_sync", self.stream)
+        t, _, V, G = self.model.appearance()
+        return api.to_numpy(t, (V, G))
+
+    def save_appearance(self):
+        """--appearance-dim: the table as appearance.npy, wherever poses_refined.npy goes (a checkpoint does not hold
+        it)"""
+        if self.app_adam is None or self.rank != 0:
+            return
+        d = self.ckpt_dir or "."
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "appearance.npy"), self.appearance())
 
     def save_poses(self):
         """--refine-poses: the refined pose table [V, 12] as poses_refined.npy next to the checkpoints (a checkpoint
@@ -362,6 +403,13 @@ def parse_args(argv=None):
                          "the ball of radius 2 before it is encoded.  Cameras are expected inside the unit ball (scale the "
                          "poses accordingly); --lindisp with a large far plane goes with it.  Needs the any-shape path, as "
                          "--refine-poses does")
+    ap.add_argument("--appearance-dim", type=int, default=0, metavar="G",
+                    help="--scene: a learned appearance vector of G floats per training image (NeRF-W / mip-NeRF 360's "
+                         "GLO vectors), fed to the view-dependent branch: absorbs per-image exposure and white balance; "
+                         "writes appearance.npy into --ckpt-dir (default: the working directory); held-out views are "
+                         "rendered with the neutral (zero) vector.  Needs the any-shape path, as --refine-poses does")
+    ap.add_argument("--appearance-lr", type=float, default=1e-3, metavar="LR",
+                    help="with --appearance-dim: the constant Adam learning rate of the appearance table")
     # the test split (Config.LlffHold / GcEvery, TrainState.cs:53,63): held-out views rendered and scored on the device
     ap.add_argument("--holdout", type=int, default=0, metavar="N",
                     help="--scene: hold out every N-th view (i %% N == 0) as the test split; evaluated at the end")
@@ -376,6 +424,10 @@ def parse_args(argv=None):
         ap.error("--distortion-loss-mult must be a finite number >= 0")
     if not (a.interlevel_loss_mult >= 0 and a.interlevel_loss_mult < float("inf")):
         ap.error("--interlevel-loss-mult must be a finite number >= 0")
+    if a.appearance_dim < 0 or a.appearance_dim > 256:
+        ap.error("--appearance-dim must be in [0, 256]")
+    if not (a.appearance_lr > 0 and a.appearance_lr < float("inf")):
+        ap.error("--appearance-lr takes a learning rate > 0")
     if a.refine_poses and not a.scene:
         ap.error("--refine-poses needs --scene: only a scene of poses and images has poses to refine")
     if a.holdout < 0 or a.holdout == 1:
@@ -411,13 +463,15 @@ def main(argv=None):
                      ckpt_dir=a.ckpt_dir, sync_check_every=a.sync_check_every,
                      grad_max_norm=a.grad_max_norm, grad_max_val=a.grad_max_val, weight_decay_mult=a.weight_decay,
                      stats=a.stats, refine_poses=a.refine_poses, interlevel_loss_mult=a.interlevel_loss_mult,
-                     contract=a.contract, lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
+                     contract=a.contract, appearance_dim=a.appearance_dim, appearance_lr=a.appearance_lr, lr_init=a.lr_init, lr_delay_steps=a.lr_delay_steps,
                      precision=PRECISION_NAMES[a.precision], **net)
     except NofError as e:
         if a.refine_poses and e.status == 5:  # NOF_ERR_UNSUPPORTED: the library says what --refine-poses needs
             raise SystemExit(f"--refine-poses: {e}")
         if a.contract and e.status == 5:
             raise SystemExit(f"--contract: {e}")
+        if a.appearance_dim and e.status == 5:
+            raise SystemExit(f"--appearance-dim: {e}")
         raise
     if a.resume:
         tr.resume(a.resume)
@@ -446,6 +500,7 @@ def main(argv=None):
 
     torch.cuda.synchronize()
     tr.save_poses()
+    tr.save_appearance()
     dt = time.perf_counter() - t0
     print(f"{a.steps} steps in {dt:.3f} s: {a.steps * a.batch / dt:.1f} rays/s", flush=True)
 
