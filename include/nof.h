@@ -286,6 +286,21 @@ nof_status nof_mipnerf_interlevel_loss(nof_mipnerf* h, float* out);
 enum { NOF_CONTRACT_NONE = 0, NOF_CONTRACT_SPHERE = 1 };
 nof_status nof_mipnerf_set_contraction(nof_mipnerf* h, int32_t mode);
 nof_status nof_mipnerf_get_contraction(nof_mipnerf* h, int32_t* mode);
+/* Diagnostic: which of the fused 8x256 training step's launch fusions are in force.  Bit flags, all
+ * on by default; clearing one runs that part the unfused way.  It never changes a result: gradients, parameters,
+ * colours and the loss are bit for bit the same at every setting, which is what the A/B measurements and
+ * tests/test_gpu_step_fusion.py rely on.
+ *   NOF_STEP_FUSION_BWD_PAIR   fp32 / f16x2 / f16split: the dX chains of a pair of levels in ONE k_mlp_bwd16 launch
+ *                              (both gradient entries; nof_mlp_get_gradient, one level per call, always launches
+ *                              per level); cleared: one launch per level.
+ *   NOF_STEP_FUSION_VIEW_TABLES  the same modes: the step's pack launch writes every ray's view-PE row and
+ *                              view-layer bias b9 + W9[:, 256:283] PE(d) once, and k_mlp_fwd16 reads them; cleared:
+ *                              every wave of every level computes its ray's in the kernel's prologue, as
+ *                              nof_mlp_get_output and nof_mipnerf_render_device always do.
+ * Takes effect from the next call, allocates nothing, is not held by checkpoints.  Unknown bits:
+ * NOF_ERR_INVALID_ARG.  Any-shape objects and the F16 / split modes accept it and ignore it. */
+enum { NOF_STEP_FUSION_BWD_PAIR = 1, NOF_STEP_FUSION_VIEW_TABLES = 2, NOF_STEP_FUSION_ALL = 3 };
+nof_status nof_mipnerf_set_step_fusion(nof_mipnerf* h, uint32_t flags);
 /* Per-view appearance embeddings (NeRF-W / mip-NeRF 360's GLO vectors; no counterpart in the reference; DESIGN.md
  * 6j).  With appearance_views = V and appearance_dim = G > 0 the model owns a zero-initialised fp32 table E [V][G]
  * outside the parameter arena, and the view layer (layer net_depth + 1) has in = W + Vd + G: its input for every

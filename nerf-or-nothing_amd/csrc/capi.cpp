@@ -302,6 +302,12 @@ nof_status nof_mipnerf_set_contraction(nof_mipnerf* h, int32_t mode) {
     h->impl->set_contraction(mode);
   });
 }
+nof_status nof_mipnerf_set_step_fusion(nof_mipnerf* h, uint32_t flags) {
+  return guard([&] {
+    ARG(h && (flags & ~(uint32_t)NOF_STEP_FUSION_ALL) == 0);
+    h->impl->mlp->set_step_fusion(flags);
+  });
+}
 nof_status nof_mipnerf_get_contraction(nof_mipnerf* h, int32_t* mode) {
   return guard([&] { ARG(h && mode); *mode = h->impl->contraction(); });
 }

@@ -242,6 +242,8 @@ AcceleratedMLP::AcceleratedMLP(int deg_point, int deg_view, const nof_config& cf
     NOF_HIP(hipMemset(L.delta9x.p, 0, L.delta9x.n * sizeof(float)));  // rows 132..159 stay zero
     max_M_ = std::max(max_M_, L.cap);
   }
+  view_pe_.alloc((size_t)cfg.max_rays * 32);
+  view_bias_.alloc((size_t)cfg.max_rays * 128);
   slab_cap_ = (size_t)(num_cu_ + 64) * 65536;
   slabs_.alloc(slab_cap_);
   bias_slabs_.alloc((size_t)(num_cu_ + 64) * 256);
@@ -254,7 +256,9 @@ std::vector<int> AcceleratedMLP::get_layer_sizes() const {
   return s;
 }
 
-bool AcceleratedMLP::pack_weights(const nof::StratArgs* strat) {
+bool AcceleratedMLP::pack_weights(const nof::StratArgs* strat, const float* view_dirs, int view_n) {
+  view_dirs_ = nullptr;  // the tables of an earlier step are stale: the weights may have moved
+  view_n_ = 0;
   if (generic_) {  // the any-shape path reads the canonical arena directly
     if (f16_products()) {  // the step's delta-scale maxima start at 0
       NOF_HIP(hipMemsetAsync(amax_.p, 0, lv_.size() * sizeof(uint32_t), st_));
@@ -271,6 +275,14 @@ bool AcceleratedMLP::pack_weights(const nof::StratArgs* strat) {
     pa.nzero = (int)lv_.size();
     amax_cleared_ = (1u << lv_.size()) - 1u;
     amax_given_ = 0u;
+  }
+  // the step's per-ray view tables, for the k_mlp_fwd16 modes (the split and F16 forwards have their own prologues)
+  const bool fwd16 = precision_ == NOF_PRECISION_F32 || precision_ == NOF_PRECISION_F16X2 ||
+                     precision_ == NOF_PRECISION_F32_F16SPLIT;
+  if (view_dirs && view_n > 0 && view_n <= cfg_.max_rays && fwd16 && (step_fusion_ & NOF_STEP_FUSION_VIEW_TABLES)) {
+    pa.view.n = view_n; pa.view.dirs = view_dirs; pa.view.pe = view_pe_.p; pa.view.bias = view_bias_.p;
+    view_dirs_ = view_dirs;
+    view_n_ = view_n;
   }
   tb(kTPack);
   if (precision_ == NOF_PRECISION_F16)
@@ -336,6 +348,10 @@ void AcceleratedMLP::forward_fused(int level, int n, int samples, const float* t
   a.no_store = inference ? 1 : 0;
   a.cylinder = cfg_.ray_shape == NOF_RAY_CYLINDRICAL ? 1 : 0;
   a.t = t; a.origins = origins; a.dirs = dirs; a.radii = radii;
+  if (view_dirs_ && view_dirs_ == dirs && n <= view_n_) {  // this step's pack launch tabulated these rays
+    a.view_pe = view_pe_.p;
+    a.view_bias = view_bias_.p;
+  }
   run_forward(level, a);
 }
 
@@ -745,8 +761,9 @@ void AcceleratedMLP::run_backward(int level, const float* color_grad, const floa
   te(kTMlpBwd);
 }
 
-// F16: two levels' dX chains as ONE persistent launch (level 0's groups, then level 1's; the same
-// arithmetic per group as two launches)
+// Two levels' dX chains as ONE launch (the same arithmetic per group as two launches).  F16: a persistent grid
+// over level 0's groups, then level 1's; fp32 / f16x2 / f16split (k_mlp_bwd16): level 1's workgroups after level
+// 0's on the grid, so the CUs are drained and refilled once per pair instead of once per level
 void AcceleratedMLP::run_backward2(int level, const float* const* color_grads, const float* const* density_grads) {
   nof::BwdArgs b = bwd_args(level, color_grads[0], density_grads[0]);
   const nof::BwdArgs b1 = bwd_args(level + 1, color_grads[1], density_grads[1]);
@@ -815,7 +832,12 @@ float* const* AcceleratedMLP::get_gradient_levels(const float* const* color_grad
   else
     for (int b = 0; b < kBuckets; ++b) (void)schedule(0, nl, b);
   int l = 0;
-  if (precision_ == NOF_PRECISION_F16)  // levels in pairs: one persistent backward launch per pair
+  // levels in pairs, one backward launch per pair: F16 always (its persistent grid), the k_mlp_bwd16 modes unless
+  // the diagnostic switch asks for per-level launches; the split mode's k_mlp_bwd<1> takes one level
+  const bool pair16 = (step_fusion_ & NOF_STEP_FUSION_BWD_PAIR) &&
+                      (precision_ == NOF_PRECISION_F32 || precision_ == NOF_PRECISION_F16X2 ||
+                       precision_ == NOF_PRECISION_F32_F16SPLIT);
+  if (precision_ == NOF_PRECISION_F16 || pair16)
     for (; l + 1 < nl; l += 2) run_backward2(l, color_grads + l, density_grads + l);
   for (; l < nl; ++l) run_backward(l, color_grads[l], density_grads[l]);
   return wgrad_levels(0, nl, (flags & NOF_GRAD_ACCUMULATE) ? 1 : 0, buckets);
@@ -1398,7 +1420,7 @@ float* const* AcceleratedMipNeRF::run(int n, const float* o, const float* d, con
   nof::StratArgs sa;  // level 0's t-values, by the pack launch's extra blocks
   sa.n = n; sa.S = cfg_.num_samples[0]; sa.nears = nears; sa.fars = fars; sa.randomized = cfg_.randomized;
   sa.lindisp = cfg_.lindisp; sa.seed = seed_; sa.step = step_; sa.ray_base = ray_base_; sa.t = t_[0].p;
-  const bool sampled = mlp->pack_weights(&sa);
+  const bool sampled = mlp->pack_weights(&sa, d, n);  // (+ the step's per-ray view tables)
   for (int lv = 0; lv < L; ++lv) {  // MNcpp:85-123
     TraceRange lr(kFwd[lv & 3]);
     const int S = cfg_.num_samples[lv];

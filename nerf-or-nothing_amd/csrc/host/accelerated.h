@@ -145,8 +145,11 @@ class AcceleratedMLP {
   void forward_fused(int level, int n, int samples, const float* t, const float* origins, const float* dirs,
                      const float* radii, bool inference = false);
   // rebuild the packed weight images from the canonical arena; strat (optional): level 0's stratified sampling
-  // run by the same launch — returns whether it did (no pack launch on the any-shape path)
-  bool pack_weights(const nof::StratArgs* strat = nullptr);
+  // run by the same launch — returns whether it did (no pack launch on the any-shape path).  view_dirs [view_n][3]
+  // (optional): the same launch also tabulates these rays' view-PE rows and view-layer biases (launch.h
+  // ViewTabArgs) in the k_mlp_fwd16 modes, and forward_fused on the same direction pointer reads them until the
+  // next pack_weights; every other forward computes them in its prologue
+  bool pack_weights(const nof::StratArgs* strat = nullptr, const float* view_dirs = nullptr, int view_n = 0);
   const float* density(int level) const { return lv_[level].sigma.p; }
   const float* rgb(int level) const { return lv_[level].rgb.p; }
   KernelTimer* timer = nullptr;
@@ -214,6 +217,10 @@ class AcceleratedMLP {
   void set_appearance_job(const int32_t* ids, int accumulate, int levels) {
     app_job_ = AppJob{ids, accumulate, levels, true};
   }
+  // Diagnostic (include/nof.h nof_mipnerf_set_step_fusion): NOF_STEP_FUSION_* bits, all on by default; a cleared
+  // bit runs the step the unfused way, with the same results bit for bit
+  void set_step_fusion(uint32_t flags) { step_fusion_ = flags; }
+  uint32_t step_fusion() const { return step_fusion_; }
 
  private:
   struct AppJob {
@@ -257,6 +264,12 @@ class AcceleratedMLP {
   hipStream_t st_;
   int num_cu_ = 256;
   int precision_ = 0;  // NOF_PRECISION_*
+  // (a diagnostic build may start from another default: make VARIANT=... DIAG=-DNOF_STEP_FUSION_DEFAULT=<bits>, so
+  // that an unmodified benchmark measures one fusion at a time)
+#ifndef NOF_STEP_FUSION_DEFAULT
+#define NOF_STEP_FUSION_DEFAULT NOF_STEP_FUSION_ALL
+#endif
+  uint32_t step_fusion_ = NOF_STEP_FUSION_DEFAULT;
   // fp16 (hi, lo) MFMA pieces in the forward / dX chain (F16X2, F32_F16SPLIT): f16 weight images,
   // power-of-2 scaled deltas
   bool f16_pieces() const {
@@ -331,6 +344,9 @@ class AcceleratedMLP {
   static void gen_split(int nout, int ncols, int M, int* ksplit, int* kchunk);
   float* const* gen_publish(bool buckets);  // the bucket hook once per bucket (every gradient is final)
   DevBuf<float> params_, grads_, wimg_f_, wimg_b_;
+  DevBuf<float> view_pe_, view_bias_;   // the step's view tables [max_rays][32], [max_rays][128] (fused path)
+  const float* view_dirs_ = nullptr;    // the directions the last pack launch tabulated (null: none)
+  int view_n_ = 0;
   std::vector<float*> param_views_, grad_views_;
   std::vector<Level> lv_;
   int max_M_ = 0;

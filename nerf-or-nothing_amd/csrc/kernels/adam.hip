@@ -5,6 +5,7 @@
 // (adam_optimizer_step AF:403-416, D18): eps inside 1/sqrt, fp32, contraction off, so the
 // result is bit-identical to oracle/oracle.cpp::orc_adam_step.
 #include "common.h"
+#include "geometry.h"
 #include "launch.h"
 #include "resample.h"
 #include "mlp_common.h"
@@ -16,6 +17,8 @@ namespace nof {
 
 // 256-thread blocks the pack launch appends for PackArgs::strat (0 when it carries none)
 static int strat_blocks(const StratArgs& z) { return z.n > 0 ? (z.n * (z.S + 1) + 255) / 256 : 0; }
+// and for PackArgs::view: two rays per block
+static int view_blocks(const ViewTabArgs& v) { return v.n > 0 ? (v.n + 1) / 2 : 0; }
 
 __global__ void k_adam(int64_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, float lr, float inv1, float inv2) {
@@ -218,16 +221,46 @@ __device__ inline void bwd_slice(int s, int& l, int& o) {
   else { l = 7 - (s - 4) / 8; o = 32 * ((s - 4) % 8); }
 }
 
+// The blocks a pack launch carries past its own (launch.h PackArgs): level 0's stratified sampling, then the per-ray
+// view tables.  Returns whether this block was one of them.  A view block serves two rays, 128 threads each: thread
+// o < 32 evaluates view-PE feature o (zeros from 27 on), then every thread chains one output of the view bias over
+// the ray's 27 values — from the canonical arena P, in k_mlp_fwd16's order, with explicit FMAs.
+__device__ inline bool pack_extra_block(const float* __restrict__ P, const PackArgs& pa) {
+  const int xb = (int)blockIdx.x - pa.pack_blocks;
+  if (xb < 0) return false;
+  if (xb < pa.strat_blocks) {  // the step's level-0 sampling (PackArgs::strat)
+    const StratArgs& z = pa.strat;
+    stratified_t(xb * (int)blockDim.x + (int)threadIdx.x, z.n, z.S, z.nears, z.fars, z.randomized, z.lindisp, z.seed,
+                 z.step, 0, z.ray_base, z.t);
+    return true;
+  }
+  __shared__ float pe_s[2][32];
+  const ViewTabArgs& v = pa.view;
+  const int sub = (int)threadIdx.x >> 7, o = (int)threadIdx.x & 127;
+  const int ray = 2 * (xb - pa.strat_blocks) + sub;
+  const bool live = ray < v.n;  // (an odd ray count: the last block's second half idles, but joins the barrier)
+  if (live && o < 32) {
+    const float d3[3] = {v.dirs[3 * ray], v.dirs[3 * ray + 1], v.dirs[3 * ray + 2]};
+    const float f = o < kDirIn ? dir_feature(o, d3) : 0.0f;
+    pe_s[sub][o] = f;
+    v.pe[(size_t)ray * 32 + o] = f;
+  }
+  __syncthreads();
+  if (live) {
+    float s = P[pa.boff[9] + o];
+    const float* w9 = P + pa.woff[9] + (int64_t)o * 283 + 256;
+#pragma unroll
+    for (int k = 0; k < kDirIn; ++k) s = __builtin_fmaf(w9[k], pe_s[sub][k], s);
+    v.bias[(size_t)ray * 128 + o] = s;
+  }
+  return true;
+}
+
 // One thread per image float.  Forward slice element (row r, col c) = W_l[r][col + c];
 // backward slice element (row i, col c) = W_l[o + c][i]; both stored at slice_off(r, c).
 __global__ void k_pack_weights(const float* __restrict__ P, PackArgs pa, float* __restrict__ wf,
                                float* __restrict__ wb) {
-  if ((int)blockIdx.x >= pa.pack_blocks) {  // the step's level-0 sampling (PackArgs::strat)
-    const StratArgs& z = pa.strat;
-    stratified_t(((int)blockIdx.x - pa.pack_blocks) * (int)blockDim.x + (int)threadIdx.x, z.n, z.S, z.nears, z.fars,
-                 z.randomized, z.lindisp, z.seed, z.step, 0, z.ray_base, z.t);
-    return;
-  }
+  if (pack_extra_block(P, pa)) return;  // (block-uniform)
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nf = (int64_t)kFwdImageFloats, nb = (int64_t)kBwdImageFloats;
   if (gid < nf) {
@@ -306,12 +339,7 @@ __device__ inline typename SplitMode<P>::V2 split_piece2(float w, int piece) {
 template <int P>
 __global__ void k_pack_weights_x3(const float* __restrict__ P_, PackArgs pa, float* __restrict__ wf,
                                   float* __restrict__ wb) {
-  if ((int)blockIdx.x >= pa.pack_blocks) {  // the step's level-0 sampling (PackArgs::strat)
-    const StratArgs& z = pa.strat;
-    stratified_t(((int)blockIdx.x - pa.pack_blocks) * (int)blockDim.x + (int)threadIdx.x, z.n, z.S, z.nears, z.fars,
-                 z.randomized, z.lindisp, z.seed, z.step, 0, z.ray_base, z.t);
-    return;
-  }
+  if (pack_extra_block(P_, pa)) return;  // (block-uniform)
   constexpr int NP = SplitMode<P>::NP;
   constexpr int kChunks = split_slice_floats<P>() / 4;  // fragments of 16 B per slice
   const float* __restrict__ Pp = P_;
@@ -359,7 +387,8 @@ hipError_t launch_pack_weights_x3(const float* params, const PackArgs& pa, float
   const int64_t total = (int64_t)(kFwdSlices + kBwdSlices) * chunks + kFwdTail + kBwdTail;
   PackArgs a = pa;
   a.pack_blocks = (int)((total + 255) / 256);
-  const dim3 grid((unsigned)(a.pack_blocks + strat_blocks(pa.strat)));
+  a.strat_blocks = strat_blocks(pa.strat);
+  const dim3 grid((unsigned)(a.pack_blocks + a.strat_blocks + view_blocks(pa.view)));
   if (precision == 2) hipLaunchKernelGGL(k_pack_weights_x3<2>, grid, dim3(256), 0, st, params, a, wimg_f, wimg_b);
   else hipLaunchKernelGGL(k_pack_weights_x3<1>, grid, dim3(256), 0, st, params, a, wimg_f, wimg_b);
   return hipGetLastError();
@@ -437,8 +466,9 @@ hipError_t launch_pack_weights(const float* params, const PackArgs& pa, float* w
   const int64_t total = (int64_t)kFwdImageFloats + (int64_t)kBwdImageFloats;
   PackArgs a = pa;
   a.pack_blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)(a.pack_blocks + strat_blocks(pa.strat))), dim3(256), 0, st,
-                     params, a, wimg_f, wimg_b);
+  a.strat_blocks = strat_blocks(pa.strat);
+  hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)(a.pack_blocks + a.strat_blocks + view_blocks(pa.view))),
+                     dim3(256), 0, st, params, a, wimg_f, wimg_b);
   return hipGetLastError();
 }
 

@@ -186,6 +186,10 @@ struct FwdArgs {
   float dbias = -1.0f, rgb_scale = 1.002f, rgb_pad = 0.001f;
   const float *t, *origins, *dirs, *radii;  // fused-encoding inputs
   const float *enc_pos, *enc_dir;          // encoded inputs (API path): [M][96], [n][27]
+  // k_mlp_fwd16, fused encoding only (optional, both or neither): the step's per-ray view tables (ViewTabArgs,
+  // written by the pack launch) — the view-PE rows [n][32] and the view layer's per-ray bias [n][128]; null: every
+  // wave computes its ray's from dirs and the image's tail (the same bits)
+  const float *view_pe, *view_bias;
   const float* wimg;                       // packed forward image (slices + tail)
   float* act_in;   // [M/32][128][32]
   float* act_h;    // [8][M/32][256][32]
@@ -507,13 +511,25 @@ struct StratArgs {
   uint32_t step = 0, ray_base = 0;
   float* t = nullptr;
 };
+// the step's per-ray view tables (k_mlp_fwd16's FwdArgs::view_pe / view_bias), computable by the pack launch's
+// extra blocks from the canonical parameter arena (not from the image the same launch is writing):
+//   pe[r][k]   = dir_feature(k, dirs[r]) for k < 27, 0 for k = 27..31  (act_in rows 96..127 of the ray's samples)
+//   bias[r][o] = fma chain s = b9[o]; s = fmaf(W9[o][256 + k], pe[r][k], s), k = 0..26 ascending
+// — the values and the rounding order of k_mlp_fwd16's own prologue, which every wave of every level repeats
+struct ViewTabArgs {
+  int n = 0;  // rays (0: none)
+  const float* dirs = nullptr;
+  float *pe = nullptr, *bias = nullptr;
+};
 struct PackArgs {
   int woff[11]; int boff[11];
   uint32_t* zero = nullptr; int nzero = 0;  // words the pack launch also clears (the f16 modes' delta-scale maxima)
   // the training step's level-0 sampling rides the pack launch (blocks past the pack's own: one launch fewer
-  // per step; the launch wrappers set pack_blocks)
+  // per step; the launch wrappers set pack_blocks), and so do the view tables (launch_pack_weights and
+  // launch_pack_weights_x3 only: blocks past the sampling's, the wrappers set strat_blocks)
   StratArgs strat;
-  int pack_blocks = 0;
+  ViewTabArgs view;
+  int pack_blocks = 0, strat_blocks = 0;
 };
 hipError_t launch_pack_weights(const float* params, const PackArgs& pa, float* wimg_f, float* wimg_b, hipStream_t st);
 // split images: precision 1 (bf16 hi/mid/lo) or 2 (f16 hi/lo)

@@ -102,17 +102,48 @@ __global__ __launch_bounds__(kMlp16Threads, 1) void k_mlp_fwd16(FwdArgs a) {
   // whole 32-sample blocks of one ray each, the block inside the launch
   NOF_DCHECK(a.M % kBlk == 0 && a.S % kBlk == 0 && blk >= 0 && blk < nblk, kChkMlpBlock);
 
+  // ---- prologue.  vmcnt retires in issue order, so a wait for any value loaded AFTER the ring DMA would wait for
+  // the DMA's 64 KB first, and a barrier that waits for everything (__syncthreads: vmcnt(0)) would also wait for the
+  // HBM acknowledgement of the act_in stores, which nothing in this kernel reads.  Hence this order:
+  //   1. every load whose value the prologue needs (t, the view tables, the bias / w8 table), into registers;
+  //   2. the ring DMA of slices 0 and 1;
+  //   3. the encodings, computed while the DMA is in flight; the tables written to LDS;
+  //   4. the act_in stores, last;
+  //   5. a counted wait (below) and the barrier.
+  // (The encoded path and the in-kernel view work load more after the DMA; their waits then cover it: API paths.)
+  const bool vtab = a.view_pe != nullptr;  // launch-uniform
+  float t01[2] = {0.0f, 0.0f};
+  float d3[3] = {0.0f, 0.0f, 0.0f}, o3[3] = {0.0f, 0.0f, 0.0f}, radius = 0.0f;
+  if (!a.encoded) {
+    const float* tr = a.t + (size_t)ray * (a.S + 1) + s0 + j;
+    t01[0] = tr[0]; t01[1] = tr[1];
+    d3[0] = a.dirs[3 * ray]; d3[1] = a.dirs[3 * ray + 1]; d3[2] = a.dirs[3 * ray + 2];
+    o3[0] = a.origins[3 * ray]; o3[1] = a.origins[3 * ray + 1]; o3[2] = a.origins[3 * ray + 2];
+    radius = a.radii[ray];
+  }
+  f32x4 vpe[2] = {};
+  float vb[2] = {0.0f, 0.0f};
+  if (vtab) {  // feat16(t, g, r) - 96 = 16 (t - 6) + 4 g + r: one 16-byte load per act_in tile 6, 7
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      vpe[u] = *reinterpret_cast<const f32x4*>(a.view_pe + (size_t)ray * 32 + (feat16(6 + u, g, 0) - kPosIn));
+#pragma unroll
+    for (int rep = 0; rep < 2; ++rep) vb[rep] = a.view_bias[(size_t)ray * 128 + lane + 64 * rep];
+  }
+  // trunk biases (layers 0..7) and w8: 576 16-byte chunks, one per thread and a second one in wave 0
+  static_assert(kBiasLds / 4 > kMlp16Threads && kBiasLds / 4 <= kMlp16Threads + 64, "bias table: wave 0 takes the rest");
+  const f32x4 tab0 = *reinterpret_cast<const f32x4*>(tail + kFwdTailBias + 4 * tid);
+  f32x4 tab1 = {};
+  if (wave == 0) tab1 = *reinterpret_cast<const f32x4*>(tail + kFwdTailW8 + 4 * tid);
+  __builtin_amdgcn_sched_barrier(0);
   ring16_prologue(a.wimg, lds, tid);  // first two slices in flight while the encodings are computed
+  __builtin_amdgcn_sched_barrier(0);
 
   // ---- encodings: IPE feature 16t + 4g + r in ipe[t][r] (the B-operand order) ---------------
   float ipe[6][4];
-  float d3[3];
   if (!a.encoded) {
-    d3[0] = a.dirs[3 * ray]; d3[1] = a.dirs[3 * ray + 1]; d3[2] = a.dirs[3 * ray + 2];
-    const float o3[3] = {a.origins[3 * ray], a.origins[3 * ray + 1], a.origins[3 * ray + 2]};
-    const float* tr = a.t + (size_t)ray * (a.S + 1) + s0 + j;
     float mean[3], cov[3];
-    frustum_gaussian(tr[0], tr[1], o3, d3, a.radii[ray], mean, cov, a.cylinder != 0);
+    frustum_gaussian(t01[0], t01[1], o3, d3, radius, mean, cov, a.cylinder != 0);
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
@@ -123,32 +154,25 @@ __global__ __launch_bounds__(kMlp16Threads, 1) void k_mlp_fwd16(FwdArgs a) {
     for (int t = 0; t < 6; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) ipe[t][r] = a.enc_pos[(size_t)m * kPosIn + feat16(t, g, r)];
-  }
-  // view PE of the wave's ray: lane k < 27 evaluates feature k once, every lane reads the 27 values
-  // back as wave-uniform scalars (27 accurate sin/cos per lane otherwise, MFMA-idle prologue time)
-  const int kl = lane < kDirIn ? lane : 0;
-  const float pe_l = a.encoded ? a.enc_dir[(size_t)ray * kDirIn + kl] : dir_feature(kl, d3);
-  float pe[kDirIn];
-#pragma unroll
-  for (int k = 0; k < kDirIn; ++k) pe[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pe_l), k));
-
-  const ST bst(lane, half);
-  if constexpr (store) {
-    const __amdgpu_buffer_rsrc_t act_in_rs = blk_rsrc_t(reinterpret_cast<AE*>(a.act_in) + (size_t)blk * kInF * kBlk);
+    // consumed inside the branch: loads left in flight across the join would make the fused path's first register
+    // reuse wait for "them" with a full vmcnt(0), that is for its ring DMA
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) bst.store(act_in_rs, t, r, ipe[t][r]);
+      for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(ipe[t][r]));
+  }
+  // The view direction's work, per ray: the 27 view-PE values (act_in rows 96..122, zero rows 123..127) and the
+  // view layer's per-ray bias b9 + W9[:, 256:283] . PE(d).  With the step's view tables (FwdArgs::view_pe /
+  // view_bias, written once per step by the pack launch in this order of operations) a wave only reads its ray's
+  // rows (above); without them (the encoded path, the render path) it computes them here: lane k < 27 evaluates
+  // feature k once, every lane reads the 27 values back as wave-uniform scalars (27 accurate sin/cos per lane
+  // otherwise, MFMA-idle prologue time).  Both give the same bits.
+  float pe[kDirIn];
+  if (!vtab) {
+    const int kl = lane < kDirIn ? lane : 0;
+    const float pe_l = a.encoded ? a.enc_dir[(size_t)ray * kDirIn + kl] : dir_feature(kl, d3);
 #pragma unroll
-    for (int t = 6; t < 8; ++t)  // view PE rows 96..122, zero rows 123..127
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k = feat16(t, g, r) - kPosIn;
-        float v = 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < kDirIn; ++kk) v = (kk == k) ? pe[kk] : v;
-        bst.store(act_in_rs, t, r, v);
-      }
+    for (int k = 0; k < kDirIn; ++k) pe[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pe_l), k));
   }
   // B operand of layer 0 and the skip layer: the registers themselves, or the wave's LDS copy
   const float* ipe_b = &ipe[0][0];
@@ -162,23 +186,67 @@ __global__ __launch_bounds__(kMlp16Threads, 1) void k_mlp_fwd16(FwdArgs a) {
     }
     ipe_b = ipe_lds;
   }
-  // view-direction part of layer 9 folded into a per-ray bias: b9 + W9[:, 256:283] . PE(d)
-  float* dirb = lds + kRing + kIpeLds + wave * 128;
+  float* dirb = lds + kRing + kIpeLds + wave * 128;   // the wave's ray's view bias
   float* bias_lds = lds + kRing + kIpeLds + 8 * 128;  // trunk biases (layers 0..7) and w8
-  for (int i = tid; i < kBiasLds / 4; i += kMlp16Threads) {
-    const float* src = i < 512 ? tail + kFwdTailBias + 4 * i : tail + kFwdTailW8 + 4 * (i - 512);
-    *reinterpret_cast<f32x4*>(bias_lds + 4 * i) = *reinterpret_cast<const f32x4*>(src);
-  }
+  *reinterpret_cast<f32x4*>(bias_lds + 4 * tid) = tab0;
+  if (wave == 0) *reinterpret_cast<f32x4*>(bias_lds + 4 * (kMlp16Threads + tid)) = tab1;
+  if (vtab) {
 #pragma unroll
-  for (int rep = 0; rep < 2; ++rep) {
-    const int o = lane + 64 * rep;
-    float s = tail[kFwdTailBias + 9 * 256 + o];
-    const float* w9 = tail + kFwdTailW9d + o * 32;
+    for (int rep = 0; rep < 2; ++rep) dirb[lane + 64 * rep] = vb[rep];
+  } else {
 #pragma unroll
-    for (int k = 0; k < kDirIn; ++k) s = __builtin_fmaf(w9[k], pe[k], s);
-    dirb[o] = s;
+    for (int rep = 0; rep < 2; ++rep) {
+      const int o = lane + 64 * rep;
+      float s = tail[kFwdTailBias + 9 * 256 + o];
+      const float* w9 = tail + kFwdTailW9d + o * 32;
+#pragma unroll
+      for (int k = 0; k < kDirIn; ++k) s = __builtin_fmaf(w9[k], pe[k], s);
+      dirb[o] = s;
+    }
   }
-  __syncthreads();
+
+  const ST bst(lane, half);
+  if constexpr (store) {
+    float vrow[2][4];  // the lane's values of act_in tiles 6, 7: view-PE rows 96..122, zero rows 123..127
+    if (vtab) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vrow[u][r] = vpe[u][r];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int k = feat16(6 + u, g, r) - kPosIn;
+          float v = 0.0f;
+#pragma unroll
+          for (int kk = 0; kk < kDirIn; ++kk) v = (kk == k) ? pe[kk] : v;
+          vrow[u][r] = v;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the stores stay behind everything above, in one straight line
+    const __amdgpu_buffer_rsrc_t act_in_rs = blk_rsrc_t(reinterpret_cast<AE*>(a.act_in) + (size_t)blk * kInF * kBlk);
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bst.store(act_in_rs, t, r, ipe[t][r]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bst.store(act_in_rs, 6 + u, r, vrow[u][r]);
+    // The barrier that publishes the ring's slots 0 and 1, the bias table, dirb (and the IPE copy).  Issue order
+    // of this wave's vector-memory operations: the table loads, the 8 ring DMA steps, (API paths: more loads), then
+    // the kActInStores act_in stores and nothing else.  vmcnt retires in issue order, so vmcnt(kActInStores) leaves
+    // at most those stores in flight and has retired every DMA step and load; lgkmcnt(0) retires this wave's LDS
+    // writes.  No wave reads an LDS word another wave wrote, or a ring slot, before this barrier: the first such
+    // reads are mlp_layer16's, below.  kActInStores = 32 fits the 6-bit vmcnt field (max 63).
+    constexpr int kActInStores = 8 * 4;
+    static_assert(kActInStores == 32 && kActInStores < 64, "the literal in the wait below");
+    asm volatile("s_waitcnt vmcnt(32)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  } else {
+    __syncthreads();
+  }
 
   int cur = 0;
   const float* wsrc = a.wimg;

@@ -6,6 +6,9 @@ with ``nerf-or-nothing_amd`` on ``sys.path`` (the directory name is not a Python
 """
 from ._lib import NofError, default_config, lib  # noqa: F401
 from .api import (  # noqa: F401
+    STEP_FUSION_ALL,
+    STEP_FUSION_BWD_PAIR,
+    STEP_FUSION_VIEW_TABLES,
     AcceleratedAdamOptimizer,
     AcceleratedGradientCalculator,
     AcceleratedMipNeRF,

@@ -162,6 +162,7 @@ SIGNATURES = {
     "nof_mipnerf_set_interlevel_loss": [P, F],
     "nof_mipnerf_set_contraction": [P, I32],
     "nof_mipnerf_get_contraction": [P, P],
+    "nof_mipnerf_set_step_fusion": [P, U32],
     "nof_mipnerf_interlevel_loss": [P, C.POINTER(F)],
     "nof_mipnerf_numeric_status": [P, C.POINTER(U32), I32],
     "nof_device_checks": [C.POINTER(U32), I32],

@@ -16,6 +16,11 @@ import numpy as np
 from . import _lib as L
 from ._lib import call, lib
 
+# include/nof.h NOF_STEP_FUSION_* (AcceleratedMipNeRF.set_step_fusion)
+STEP_FUSION_BWD_PAIR = 1
+STEP_FUSION_VIEW_TABLES = 2
+STEP_FUSION_ALL = 3
+
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
@@ -405,6 +410,12 @@ class AcceleratedMipNeRF:
         inside the unit ball.  A hyper-parameter (checkpoints do not hold it); any-shape path only: a fused 8x256
         model raises NofError(NOF_ERR_UNSUPPORTED)."""
         call("nof_mipnerf_set_contraction", self._h, int(mode))
+
+    def set_step_fusion(self, flags: int = STEP_FUSION_ALL) -> None:
+        """Diagnostic (include/nof.h nof_mipnerf_set_step_fusion): STEP_FUSION_* bit flags, all on by default;
+        a cleared bit runs that part of the fused 8x256 training step the unfused way.  Results are bit for bit
+        the same at every setting."""
+        call("nof_mipnerf_set_step_fusion", self._h, int(flags))
 
     def contraction(self) -> int:
         """The contraction mode in force (0 = none, 1 = sphere)."""
