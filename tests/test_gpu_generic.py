@@ -142,10 +142,13 @@ def _assert_dispatch(model, key):
 
 
 def _check(gpu, oracle, name, kind, n, samples, lindisp=0, ray_shape=0, nthreads=16, lossmult=None, heads=None,
-           regime=""):
+           regime="", params=None):
+    """params: None for the model's own Glorot draw, or a callable (oracle, spec, Glorot arena) -> arena that is
+    installed before the step (tests/param_sets.py)."""
     import torch
     import nof
     from nof import synth
+    from param_sets import install, same_bits
 
     spec = SPECS[name]
     seed, step, ray_base = 0x77, 2, 40
@@ -156,6 +159,8 @@ def _check(gpu, oracle, name, kind, n, samples, lindisp=0, ray_shape=0, nthreads
     sp = _ospec(oracle, spec)
     sizes = oracle.layer_sizes(sp)
     assert model.GetLayerSizes() == list(sizes)
+    pptr, P = model.mlp.flat_params()
+    installed = None if params is None else install(model, params(oracle, sp, nof.to_numpy(pptr, (P,))))
     r = synth.blender_rays(n, seed=23) if kind == "blender" else synth.llff_rays(n, seed=23)
     if lossmult is not None:
         r["lossmult"] = np.resize(np.asarray(lossmult, np.float32), n)
@@ -163,9 +168,9 @@ def _check(gpu, oracle, name, kind, n, samples, lindisp=0, ray_shape=0, nthreads
     torch.cuda.synchronize()
     assert len(grads) == len(sizes)
     lv = [model.level_numpy(l) for l in range(len(samples))]
-    pptr, P = model.mlp.flat_params()
     assert P == int(np.sum(sizes))
     params = nof.to_numpy(pptr, (P,))
+    assert installed is None or same_bits(params, installed), "the step changed the installed parameters"
     gptr, _ = model.mlp.flat_grads()
     G = nof.to_numpy(gptr, (P,))
     assert grads[0] == gptr

@@ -267,10 +267,13 @@ def _assert_dispatch(model, name, levels):
     assert old["k_encode_g"] + old["k_encode_g4"] == levels
 
 
-def _check(gpu, oracle, name, n, samples):
+def _check(gpu, oracle, name, n, samples, params=None):
+    """params: None for the model's own Glorot draw, or a callable (oracle, spec, Glorot arena) -> arena that is
+    installed before the step (tests/param_sets.py)."""
     import torch
     import nof
     from nof import synth
+    from param_sets import install, same_bits
 
     spec = _spec(name)
     seed, step, ray_base = 0x77, 2, 40
@@ -280,14 +283,16 @@ def _check(gpu, oracle, name, n, samples):
     sp = _ospec(oracle, spec)
     sizes = oracle.layer_sizes(sp)
     assert model.GetLayerSizes() == list(sizes)
+    pptr, P = model.mlp.flat_params()
+    installed = None if params is None else install(model, params(oracle, sp, nof.to_numpy(pptr, (P,))))
     r = synth.blender_rays(n, seed=23)
     grads = _run(model, r, gpu)
     torch.cuda.synchronize()
     assert len(grads) == len(sizes)
     assert model.numeric_status() == 0
     lv = [model.level_numpy(l) for l in range(len(samples))]
-    pptr, P = model.mlp.flat_params()
     params = nof.to_numpy(pptr, (P,))
+    assert installed is None or same_bits(params, installed), "the step changed the installed parameters"
     G = nof.to_numpy(model.mlp.flat_grads()[0], (P,))
 
     t0 = oracle.sample_stratified(r["near"], r["far"], samples[0], True, seed, step, 0, ray_base)

@@ -57,21 +57,26 @@ def test_step_parity_head_options(gpu, oracle, precision):
     _check_step(gpu, oracle, "blender", 8, (64, 128), precision, heads=dict(density_bias=0.5, rgb_padding=0.02))
 
 
-def _check_step(gpu, oracle, kind, n, samples, precision, lindisp=0, ray_shape=0, heads=None):
+def _check_step(gpu, oracle, kind, n, samples, precision, lindisp=0, ray_shape=0, heads=None, params=None):
+    """params: None for the model's own Glorot draw, or a callable (oracle, spec, Glorot arena) -> arena that is
+    installed before the step (tests/param_sets.py)."""
     import torch
     import nof
     from nof import synth
+    from param_sets import install, same_bits
 
     seed, step, ray_base = 0x1234, 3, 500
     opts = dict(lindisp=lindisp, ray_shape=ray_shape, **(heads or {}))
     model = nof.AcceleratedMipNeRF(seed=seed, max_rays=n, num_samples=samples, precision=precision, **opts)
     model.set_rng(seed, step, ray_base)
+    pptr, P = model.mlp.flat_params()
+    installed = None if params is None else install(model, params(oracle, oracle.Spec(), nof.to_numpy(pptr, (P,))))
     r = synth.blender_rays(n, seed=11) if kind == "blender" else synth.llff_rays(n, seed=11)
     grads = _run_gpu(model, r, gpu)
     torch.cuda.synchronize()
     lv = [model.level_numpy(l) for l in range(len(samples))]
-    pptr, P = model.mlp.flat_params()
     params = nof.to_numpy(pptr, (P,))
+    assert installed is None or same_bits(params, installed), "the step changed the installed parameters"
     gptr, _ = model.mlp.flat_grads()
     G = nof.to_numpy(gptr, (P,))
     assert grads[0] == gptr
